@@ -1,7 +1,12 @@
 """Consensus-fit benchmark (BASELINE.json metric) on 1..N MI355X GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line; everything in that
+line comes from the timed steps themselves.  ``--dump-outputs DIR`` also writes what the last timed
+step computed (``dump_outputs``).  ``--full`` adds the legs that take runs of their own after the
+timed steps: ``roofline_consensus`` and ``cpu_baseline``.
 
 One STEP is one full ``ConsensusClustering.fit`` of the workload (all K, all H
 resamples: resampling, batched k-means, co-sampling, co-association + histogram,
@@ -17,8 +22,8 @@ the f32-class ceiling of the f16 hi/lo MFMA scheme (2516.6 TF f16 dense / 3 = 83
 M-step's d flops per (row, running problem) update are not part of §8d's FLOP_KM; they are
 reported beside it (``mstep_flops_per_launch``, ``frac_incl_mstep``).  A fraction above 1
 means the timed launches did not do the credited work: the bench refuses to report it.
-``cpu_baseline`` times the oracle (numpy + scikit-learn, the reference's algorithm) on a
-bounded sample of the same workload on this host's usable cores and extrapolates to
+``cpu_baseline`` (``--full``) times the oracle (numpy + scikit-learn, the reference's algorithm)
+on a bounded sample of the same workload on this host's usable cores and extrapolates to
 resample-clusterings/s (rank 0, N=1 only).
 """
 from __future__ import annotations
@@ -280,19 +285,75 @@ def load_traffic(config, kernel, key="bytes_per_launch", prefix="profiles"):
     return None
 
 
+DUMP_LABEL_BYTES = 32 << 20  # cap of labels.npy; every other dumped array is a few hundred kB at most
+
+
+def dump_outputs(cc, folder):
+    """Write what the last fit left on `cc` (the arrays its caller reads) as <folder>/<name>.npy,
+    float64 unless noted, rows in K_range order:
+
+      K_range [nK]; hist, cdf [nK, 20]; bin_edges [nK, 21] float32; pac_area, cdf_area [nK];
+      delta_k [nK]; best_k [1]; pair_counts [nK, 20] (the exact integer histogram counts);
+      kmeans_inertia, kmeans_n_iter [nK, H] float32 (GPU k-means only);
+      label_rows [r] and labels [nK, r, H] float32: the label matrix (255 = not sampled) at r
+      sample rows drawn without replacement by default_rng(SEED), sorted, r as large as
+      DUMP_LABEL_BYTES allows (the whole matrix is nK x n x H bytes: 0.95 GB at C3).
+
+    The workload and every seed are fixed by the arguments, so two runs with the same arguments
+    write the same files."""
+    os.makedirs(folder, exist_ok=True)
+    Ks = list(cc.cdf_at_K_data)
+    res = [cc.cdf_at_K_data[K] for K in Ks]
+    H = int(cc.n_iterations)
+    out = {
+        "K_range": np.asarray(Ks, dtype=np.float64),
+        "hist": np.stack([np.asarray(r["hist"], dtype=np.float64) for r in res]),
+        "cdf": np.stack([np.asarray(r["cdf"], dtype=np.float64) for r in res]),
+        "bin_edges": np.stack([np.asarray(r["bin_edges"], dtype=np.float32) for r in res]),
+        "pac_area": np.asarray([cc.pac_area_[K] for K in Ks], dtype=np.float64),
+        "cdf_area": np.asarray([cc.cdf_area_[K] for K in Ks], dtype=np.float64),
+        "delta_k": np.asarray([cc.delta_k_[K] for K in Ks], dtype=np.float64),
+        "best_k": np.asarray([cc.best_k_], dtype=np.float64),
+        "pair_counts": np.stack([np.asarray(cc.pair_counts_[K], dtype=np.float64) for K in Ks]),
+    }
+    if cc.kmeans_inertia_ is not None:
+        out["kmeans_inertia"] = cc.kmeans_inertia_.cpu().numpy().astype(np.float32)
+        out["kmeans_n_iter"] = cc.kmeans_n_iter_.cpu().numpy().astype(np.float32)
+    n = cc._N
+    r = max(1, min(n, DUMP_LABEL_BYTES // (4 * len(Ks) * max(H, 1))))
+    rows = np.sort(np.random.default_rng(SEED).choice(n, size=r, replace=False))
+    rows_d = torch.from_numpy(rows).to(cc.labels_.device)
+    out["label_rows"] = rows.astype(np.float64)
+    out["labels"] = cc.labels_[:, rows_d, :H].cpu().numpy().astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, total
+    for name, a in out.items():
+        np.save(os.path.join(folder, name + ".npy"), a)
+    print(f"[bench] dumped {len(out)} arrays ({total / 1e6:.1f} MB) to {folder}", file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-consensus-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's results as DIR/<name>.npy "
+                         "(dump_outputs; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: "
+                         "roofline_consensus and cpu_baseline (one GPU, no rehearsal)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-consensus-roofline", action="store_true",
+                    help="with --full: skip roofline_consensus")
     ap.add_argument("--H", type=int, default=None, help="override n_iterations (debug runs)")
     ap.add_argument("--rehearse", default=None, metavar="R/N",
                     help="one-GPU rehearsal of rank R's share of an N-GPU fit (exchanges skipped; "
                          "the fit's results are partial, the timing is rank R's critical path)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = dict(CONFIGS[args.config])
     if args.H:
         cfg["H"] = args.H
@@ -360,6 +421,8 @@ def main():
         stats += st_i
     timers = engine.timer_summary(engine.TIMERS)
     engine.TIMERS = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(cc, args.dump_outputs)
 
     # max over ranks (wall) and sums over ranks (work, kernel time)
     vec = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -479,10 +542,10 @@ def main():
             "fit_total_ms": [round(1e3 * v, 1) for v in fit_totals],
             "partial": bool(cc.partial_),
         }
-        if world == 1 and not args.no_consensus_roofline and not args.rehearse:
+        if args.full and world == 1 and not args.no_consensus_roofline and not args.rehearse:
             # M, I and C at the config's n, capped at 50 000 (30 GB; C5's n would need 480 GB)
             out["roofline_consensus"] = consensus_roofline(dev, min(cfg["n"], 50_000), cfg["H"])
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, X)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/c4
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-timeout -k 10 600 python -u bench.py --config c4 --steps 1 --warmup 1 ${C4_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAIL; tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --config c4 --steps 1 --warmup 1 --full ${C4_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAIL; tail -5 $OUT/bench.err; exit 1; }
 echo BENCH_OK
 python -c "import json;d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1]);print(d['ms_per_step'], d['fit_timings_s'], d['kernels_ms_per_step'], d['roofline']['achieved'], d['roofline']['frac'], d['roofline']['sweeps'], d.get('cpu_baseline',{}).get('value'))"
 if [ -n "${C4_PROF:-}" ]; then

@@ -9,7 +9,7 @@ rc=$?
 echo "tests rc=$rc"; tail -25 $OUT/tests.log
 case $rc in 124|137|134|139) echo "fault/timeout: stopping"; exit $rc;; esac
 if [ -n "$NOBENCH" ]; then exit $rc; fi
-timeout -k 10 400 python -u bench.py --steps 3 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python -u bench.py --steps 3 --warmup 1 --full > $OUT/bench.json 2> $OUT/bench.err
 brc=$?
 echo "bench rc=$brc"; cat $OUT/bench.json; tail -5 $OUT/bench.err
 exit $rc

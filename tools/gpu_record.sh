@@ -10,7 +10,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -v -s --timeout 300 --timeout
 rc=$?
 echo "TESTS rc=$rc"; grep -cE "PASSED" $OUT/gpu_tests.log; grep -E "FAILED|ERROR" $OUT/gpu_tests.log | head
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAIL; tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAIL; tail -5 $OUT/bench.err; exit 1; }
 echo BENCH_OK; tail -1 $OUT/bench.json | cut -c1-400
 cd /tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o c3 --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/prof.log 2>&1 || { echo PROF_FAIL; tail -5 $OUT/prof.log; exit 1; }

@@ -17,7 +17,7 @@ if [ -n "$TESTS" ]; then
   [ $rc -eq 0 ] || exit $rc
 fi
 for c in $BENCH; do
-  timeout -k 10 ${BENCH_TIMEOUT:-600} python -u bench.py --config $c ${BENCH_ARGS:-} > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { echo "BENCH_FAIL $c"; tail -5 $OUT/bench_$c.err; exit 1; }
+  timeout -k 10 ${BENCH_TIMEOUT:-600} python -u bench.py --config $c --full ${BENCH_ARGS:-} > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { echo "BENCH_FAIL $c"; tail -5 $OUT/bench_$c.err; exit 1; }
   python -c "import json;d=json.loads(open('$OUT/bench_$c.json').read().strip().splitlines()[-1]);print('$c', round(d['value'],1), round(d['ms_per_step'],1), d['fit_timings_s'], {k: round(v,2) for k,v in d['kernels_ms_per_step'].items()}, 'km frac', d['roofline']['frac'], 'co frac', d['roofline_coassoc']['frac'], 'K4', d.get('roofline_consensus', {}).get('achieved'), d.get('roofline_consensus', {}).get('frac'))"
 done
 if [ -n "$PROF" ]; then
