@@ -25,7 +25,9 @@ infeasible at n = 50k; n_jobs / parallelization_method parallelise only the host
 foreign clusterer (``host_fit_predict``: joblib threads or processes as CC.py:185-195, with
 labels returned instead of added into a shared Mij, so nothing races; the default KMeans runs on
 the GPU whatever n_jobs says).
-Additions: ``cdf_area_``, ``delta_k_``, ``pac_area_``, ``best_k_`` and ``predict``.
+Additions: ``cdf_area_``, ``delta_k_``, ``pac_area_``, ``best_k_``, ``predict`` and Monti's item and
+cluster consensus (``consensus_sums``, ``item_consensus``, ``cluster_consensus``, ``icl``), computed
+from the label matrix without the n x n matrices (cc_item_consensus).
 """
 from __future__ import annotations
 
@@ -437,6 +439,76 @@ class ConsensusClustering:
             del D
             return post.hc_cut(K, Z[:, :2].astype(np.int64), n)
         raise ValueError(f"unknown linkage {link!r}: 'average', 'complete', 'weighted' or 'single'")
+
+    # ------------------------------------------------------------------ item / cluster consensus
+    def _icl_args(self, K, labels):
+        """(K, int64 labels [n], Kc) of the item-consensus methods, validated."""
+        if getattr(self, 'labels_', None) is None:
+            raise ValueError("fit() first")
+        K = self.best_k_ if K is None else K
+        if K not in self.cdf_at_K_data:
+            raise KeyError(f"K = {K} is not in K_range of the fit")
+        if labels is None:
+            labels = self.predict(K)
+        labels = np.asarray(labels)
+        if labels.ndim != 1 or labels.shape[0] != self._N:
+            raise ValueError(f"labels must be a 1-d array of length {self._N}, got shape {labels.shape}")
+        if labels.dtype.kind not in 'iu':
+            raise ValueError("labels must be an integer array")
+        if labels.min() < 0 or labels.max() >= KMAX:  # Kc = max + 1 <= 127 (cc_item_consensus)
+            raise ValueError(f"labels must lie in [0, {KMAX - 1}]")
+        labels = labels.astype(np.int64)
+        return K, labels, int(labels.max()) + 1
+
+    def consensus_sums(self, K=None, labels=None):
+        """int64 [n, Kc] numpy array S[i, c] = sum over j != i with labels[j] == c of
+        C_ij * 2^40, exact, for the consensus matrix C of K (default ``best_k_``) and the
+        partition ``labels`` (default ``predict(K)``; any int array of length n with values in
+        [0, 126], Kc = max + 1 <= 127, so a partition from elsewhere can be passed where ``predict`` does
+        not fit the GPU).  Computed from the fitted label matrix ``labels_`` by the tile kernel
+        cc_item_consensus: no n x n matrix is formed, whatever ``keep_matrices`` was.
+
+        Under a torch.distributed process group EVERY rank must call this method (and
+        ``item_consensus`` / ``cluster_consensus`` / ``icl``): rank r handles the tiles
+        ``dist.shard(num_tiles, r, W)`` and the int64 sums are all-reduced (SUM), so every rank
+        returns the one-rank result bit for bit."""
+        K, labels, Kc = self._icl_args(K, labels)
+        k = list(self.cdf_at_K_data).index(K)
+        L = self.labels_
+        n, Hpad = self._N, L.shape[2]
+        rank, W = dist.world()
+        t0, t1 = dist.shard(engine.num_tiles(n), rank, W)
+        S = engine.item_consensus_sums(L[k], n, Hpad, K, labels.astype(np.int32), Kc, t0, t1)
+        dist.sum_counts(S)
+        return S.cpu().numpy()
+
+    def item_consensus(self, K=None, labels=None):
+        """float64 [n, Kc]: Monti's item consensus m_i(c), the mean consensus of item i with the
+        members of cluster c other than itself (ConsensusClusterPlus calcICL's itemConsensus);
+        NaN where c has no other member.  Arguments as ``consensus_sums``."""
+        K, labels, Kc = self._icl_args(K, labels)
+        return post.item_consensus_from_sums(self.consensus_sums(K, labels), labels, Kc)
+
+    def cluster_consensus(self, K=None, labels=None):
+        """float64 [Kc]: Monti's cluster consensus m(c), the mean consensus over the pairs of
+        cluster c (calcICL's clusterConsensus); NaN for clusters with fewer than two members.
+        Arguments as ``consensus_sums``."""
+        K, labels, Kc = self._icl_args(K, labels)
+        return post.cluster_consensus_from_sums(self.consensus_sums(K, labels), labels, Kc)
+
+    def icl(self, Ks=None):
+        """{K: dict(consensus_labels, item_consensus, cluster_consensus)} for every K of the fit
+        (or the given Ks), with ``predict(K)`` as the partition: the whole of calcICL."""
+        if getattr(self, 'labels_', None) is None:
+            raise ValueError("fit() first")
+        out = {}
+        for K in (list(self.cdf_at_K_data) if Ks is None else Ks):
+            K, labels, Kc = self._icl_args(K, None)
+            S = self.consensus_sums(K, labels)
+            out[K] = dict(consensus_labels=labels,
+                          item_consensus=post.item_consensus_from_sums(S, labels, Kc),
+                          cluster_consensus=post.cluster_consensus_from_sums(S, labels, Kc))
+        return out
 
     @property
     def resampling_indices_(self):

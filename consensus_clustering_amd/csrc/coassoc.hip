@@ -1003,6 +1003,201 @@ __global__ __launch_bounds__(NT, 1) void tiles_kernel(
   }
 }
 
+// ---- item consensus sums (cc_item_consensus) -------------------------------------------------
+// S[i][c] += sum over j != i with cl[j] == c of C_ij * 2^40, for the pairs of one tile.
+// C_ij = f32(m) / f32(f64(iv) + 1e-6) with 0 <= m <= iv <= 65535 is 0 or a float32 in
+// (2^-17, 1], so C_ij * 2^40 is an integer <= 2^40 and the int64 sums over n <= 2^22 items are
+// exact and order-free (integer atomics): tile ranges, streams and ranks add to the same S.
+//
+// Main loop: the i8 one-hot contraction of tiles_kernel<KP, false> (channels padded to a power
+// of two, labels prefetched two steps ahead, the same 2 x 4 wave arrangement and accumulator
+// order), so the co-sampling counts are read back from I_tiles as the co-association epilogue
+// reads them.  Epilogue: the operand LDS becomes two u64 arrays [256][IC_CB] (row sums by the
+// cluster of the column, column sums by the cluster of the row; rows padded to IC_CS entries so
+// that the 32 columns of a wave's half land on different banks), filled with 64-bit LDS atomics
+// and flushed with one 64-bit global atomic per non-zero entry, IC_CB clusters per pass with the
+// accumulators kept in registers.  An off-diagonal tile (bi < bj) holds each pair once and adds
+// it to both sides; a diagonal tile holds the full block and adds row sums only.
+constexpr int IC_CB = 16;          // clusters per pass
+constexpr int IC_CS = IC_CB + 1;   // padded row of the LDS sums (u64 entries)
+constexpr int IC_LDS = 2 * T * IC_CS * 8 + 2 * T * 4;
+static_assert(IC_LDS <= LDS_BYTES, "the sums and the staged clusters reuse the operand LDS");
+
+template <int KP>
+__global__ __launch_bounds__(NT, 1) void item_consensus_kernel(
+    const uint8_t* __restrict__ labels, int n, int ldl, int Hpad, int64_t tile_begin,
+    const uint16_t* __restrict__ I_tiles_in, const int32_t* __restrict__ cl, int Kc,
+    unsigned long long* __restrict__ S) {
+  __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
+  static_assert(KP >= 2 && KP <= 128 && (KP & (KP - 1)) == 0, "power-of-two channels");
+  constexpr int HS = 128 / KP;  // resamples per super-step
+  constexpr int NWD = (HS + 3) / 4;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wr = wave >> 2;  // 0..1 : 128-row half
+  const int wc = wave & 3;   // 0..3 : 64-col quarter
+  const int nb = (n + T - 1) / T;
+  // the tile order of tiles_kernel (contiguous tile ranges per XCD)
+  const int nblk = static_cast<int>(gridDim.x), bx = static_cast<int>(blockIdx.x);
+  const int xq = nblk >> 3, xr = nblk & 7, xcd = bx & 7;
+  const int64_t t = tile_begin + xcd * xq + (xcd < xr ? xcd : xr) + (bx >> 3);
+  int bi, bj;
+  tile_coords(t, nb, bi, bj);
+
+  // Expansion role: one row per thread. side 0 = tile rows (A), side 1 = tile cols (B).
+  const int side = tid >> 8;
+  const int erow = tid & 255;
+  const int grow = (side ? bj : bi) * T + erow;
+  const bool evalid = grow < n;
+  const uint8_t* rowp = labels + static_cast<int64_t>(evalid ? grow : 0) * ldl;
+  const int erb = erow >> 5, er = erow & 31;
+  char* const wbase = lds + side * SIDE + erb * KC * FRAG + er * 16;
+
+  const int nsteps = Hpad / HS;
+  v16i acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = v16i{};
+
+  uint32_t w[32], wn[NWD];
+  load_labels<HS>(rowp, evalid, w);
+#pragma unroll
+  for (int kc = 0; kc < KC; ++kc) {  // step 0's one-hot straight into LDS buffer 0
+    uint32_t oc[8];
+    expand_chunk<KP>(w, kc, oc);
+#pragma unroll
+    for (int g = 0; g < 2; ++g)
+      *reinterpret_cast<uint4*>(wbase + kc * FRAG + g * 512) =
+          make_uint4(oc[g * 4 + 0], oc[g * 4 + 1], oc[g * 4 + 2], oc[g * 4 + 3]);
+  }
+  load_labels<HS>(rowp + (nsteps > 1 ? HS : 0), evalid, w);  // step 1
+  {
+    uint32_t t32[32];
+    load_labels<HS>(rowp + (nsteps > 2 ? 2 * HS : 0), evalid, t32);  // step 2
+#pragma unroll
+    for (int q = 0; q < NWD; ++q) wn[q] = t32[q];
+  }
+  __syncthreads();
+
+  for (int s = 0; s < nsteps; ++s) {
+    const char* rb = lds + (s & 1) * BUF;
+    char* wb = wbase + ((s + 1) & 1) * BUF;
+    v4i a[2][4], b[2][2];
+    auto frags = [&](int kc, v4i (&fa)[4], v4i (&fb)[2]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+        fa[mi] = *reinterpret_cast<const v4i*>(rb + ((wr * 4 + mi) * KC + kc) * FRAG + lane * 16);
+#pragma unroll
+      for (int nj = 0; nj < 2; ++nj)
+        fb[nj] = *reinterpret_cast<const v4i*>(rb + SIDE + ((wc * 2 + nj) * KC + kc) * FRAG +
+                                               lane * 16);
+    };
+    frags(0, a[0], b[0]);
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc) {
+      const int cb = kc & 1;
+      if (kc + 1 < KC) frags(kc + 1, a[cb ^ 1], b[cb ^ 1]);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int nj = 0; nj < 2; ++nj)
+          acc[mi][nj] = mfma_step<false>(a[cb][mi], b[cb][nj], acc[mi][nj]);
+      // step s+1's one-hot, chunk by chunk in the MFMA shadows (on the last step the stores
+      // land in the buffer nobody reads)
+      uint32_t oc[8];
+      expand_chunk<KP>(w, kc, oc);
+#pragma unroll
+      for (int g = 0; g < 2; ++g)
+        *reinterpret_cast<uint4*>(wb + kc * FRAG + g * 512) =
+            make_uint4(oc[g * 4 + 0], oc[g * 4 + 1], oc[g * 4 + 2], oc[g * 4 + 3]);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
+        __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);  // VALU per MFMA
+      }
+      __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);    // the 2 LDS stores
+    }
+    // rotate the label prefetch: w <- step s+2, wn <- step s+3 (clamped re-reads at the end)
+#pragma unroll
+    for (int q = 0; q < NWD; ++q) w[q] = wn[q];
+    uint32_t t32[32];
+    load_labels<HS>(rowp + ((s + 3) < nsteps ? s + 3 : s) * HS, evalid, t32);
+#pragma unroll
+    for (int q = 0; q < NWD; ++q) wn[q] = t32[q];
+    __syncthreads();
+  }
+
+  // ---- epilogue: the operand LDS is free after the loop's last barrier ----------------------
+  const int64_t tl = t - tile_begin;
+  const bool diag = (bi == bj);
+  unsigned long long* rsum = reinterpret_cast<unsigned long long*>(lds);  // [T][IC_CS] by row
+  unsigned long long* csum = rsum + T * IC_CS;                            // [T][IC_CS] by column
+  int* clr = reinterpret_cast<int*>(csum + T * IC_CS);                    // clusters of the rows
+  int* clc = clr + T;                                                     // ... of the columns
+  {
+    // an id outside [0, Kc) = no cluster: -1, which no pass matches
+    const int v = evalid ? cl[grow] : -1;
+    (side ? clc : clr)[erow] = (v >= 0 && v < Kc) ? v : -1;
+  }
+  const int rl0 = wr * 128 + 4 * (lane >> 5);  // tile-local row and column of element (0, 0, 0)
+  const int cl0 = wc * 64 + (lane & 31);
+  const uint4* it4 = reinterpret_cast<const uint4*>(I_tiles_in + tl * (T * T) + 128 * tid);
+
+  for (int c0 = 0; c0 < Kc; c0 += IC_CB) {
+    for (int e = tid; e < 2 * T * IC_CS; e += NT) rsum[e] = 0ull;
+    __syncthreads();  // (first pass: the staged clusters too)
+    // opaque per pass: the 128 pair masks and LDS addresses and the tile's 64 co-sampling
+    // dwords would otherwise be hoisted out of the pass loop and spill next to the 128
+    // accumulators
+    int rl = rl0, cc0 = cl0;
+    int zero = 0;
+    asm volatile("" : "+v"(rl), "+v"(cc0), "+v"(zero));
+    const uint4* itp = it4 + zero;
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+      for (int nj = 0; nj < 2; ++nj) {
+        asm volatile("" : "+v"(acc[mi][nj]));  // (nor the 128 fixed-point values)
+        const uint4 q0 = itp[(mi * 2 + nj) * 2], q1 = itp[(mi * 2 + nj) * 2 + 1];
+        const uint32_t iw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+        const int jl = cc0 + nj * 32;
+        const int j = bj * T + jl;
+        const uint32_t cj = static_cast<uint32_t>(clc[jl] - c0);  // column's cluster in this pass
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          const uint32_t iv = (iw[v >> 1] >> (16 * (v & 1))) & 0xFFFFu;
+          const uint32_t m = static_cast<uint32_t>(acc[mi][nj][v]);
+          const int il = rl + mi * 32 + (v & 3) + 8 * (v >> 2);
+          const int i = bi * T + il;
+          if (m != 0 && i < n && j < n && i != j) {  // m == 0: C_ij = 0 adds nothing
+            const float fi = static_cast<float>(static_cast<double>(iv) + 1e-6);
+            const float x = static_cast<float>(m) / fi;  // IEEE RN, as consensus_bin
+            const unsigned long long q =
+                static_cast<unsigned long long>(static_cast<long long>(static_cast<double>(x) * 1099511627776.0));
+            if (cj < static_cast<uint32_t>(IC_CB)) atomicAdd(&rsum[il * IC_CS + cj], q);
+            if (!diag) {
+              const uint32_t ci = static_cast<uint32_t>(clr[il] - c0);
+              if (ci < static_cast<uint32_t>(IC_CB)) atomicAdd(&csum[jl * IC_CS + ci], q);
+            }
+          }
+        }
+      }
+    __syncthreads();
+    for (int e = tid; e < 2 * T * IC_CB; e += NT) {
+      const int sd = e / (T * IC_CB), r = (e / IC_CB) % T, c = e % IC_CB;
+      const unsigned long long val = (sd ? csum : rsum)[r * IC_CS + c];
+      const int g = (sd ? bj : bi) * T + r;
+      if (val != 0ull && g < n && c0 + c < Kc)
+        atomicAdd(&S[static_cast<int64_t>(g) * Kc + c0 + c], val);
+    }
+    __syncthreads();  // the next pass clears the sums
+  }
+}
+
 __global__ void scatter_labels_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict__ lab,
                                       int H, int m, int n, uint8_t* __restrict__ out, int ldl) {
   const int64_t total = static_cast<int64_t>(H) * m;
@@ -1280,6 +1475,49 @@ extern "C" int cc_coassoc(const int8_t* labels_nh, int n, int ldl, int Hpad, int
     default: launch_tiles<128, true>(grid, st, lab, n, ldl, Hpad, tile_begin, nullptr, I_tiles, edges, bin_counts, M_full, bin_table, table_rows); break;
   }
   return launch_status("cc_coassoc");
+}
+
+extern "C" int cc_item_consensus(const int8_t* labels_nh, int n, int ldl, int Hpad, int K,
+                                 int64_t tile_begin, int64_t tile_end, const uint16_t* I_tiles,
+                                 const int32_t* cl, int Kc, int64_t* S, void* stream) {
+  int rc = check_common("cc_item_consensus", labels_nh, n, ldl, Hpad, tile_begin, tile_end);
+  if (rc) return rc;
+  if (K < 1 || K > 127 || Kc < 1 || Kc > 127) {
+    cc::set_error("cc_item_consensus: K and Kc must be in [1, 127]");
+    return CC_ERR_ARG;
+  }
+  if (n > (1 << 22)) {
+    cc::set_error("cc_item_consensus: n > 2^22 (the 2^40 fixed-point row sums must fit int64)");
+    return CC_ERR_ARG;
+  }
+  if (tile_end == tile_begin) return CC_OK;  // an empty band (a rank with no tiles)
+  if (!cl || !S || !I_tiles) {
+    cc::set_error("cc_item_consensus: I_tiles, cl and S are required");
+    return CC_ERR_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(S) & 7) || (reinterpret_cast<uintptr_t>(cl) & 3) ||
+      (reinterpret_cast<uintptr_t>(I_tiles) & 15)) {
+    cc::set_error("cc_item_consensus: S must be 8-B aligned (64-bit atomics), cl 4-B, I_tiles 16-B");
+    return CC_ERR_ARG;
+  }
+  const int64_t ntl = tile_end - tile_begin;
+  if (ntl > 0x7fffffff) {
+    cc::set_error("cc_item_consensus: too many tiles for one launch");
+    return CC_ERR_ARG;
+  }
+  const dim3 grid(static_cast<unsigned>(ntl));
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint8_t* lab = reinterpret_cast<const uint8_t*>(labels_nh);
+  unsigned long long* Su = reinterpret_cast<unsigned long long*>(S);
+  int kp = 2;  // channels padded to the next power of two (K = 1 runs as KP = 2)
+  while (kp < K) kp <<= 1;
+  switch (kp) {
+#define CC_IC(k) case k: hipLaunchKernelGGL((item_consensus_kernel<k>), grid, dim3(NT), 0, st, lab, n, ldl, Hpad, tile_begin, I_tiles, cl, Kc, Su); break;
+    CC_IC(2) CC_IC(4) CC_IC(8) CC_IC(16) CC_IC(32) CC_IC(64)
+    default: CC_IC(128)
+#undef CC_IC
+  }
+  return launch_status("cc_item_consensus");
 }
 
 #ifdef CC_CO_STAMPS

@@ -268,6 +268,46 @@ def coassoc_all(labels: torch.Tensor, n: int, Hpad: int, Ks, tile_begin: int, ti
             main.wait_stream(s)
 
 
+def item_consensus_sums(labels_nh: torch.Tensor, n: int, Hpad: int, K: int, cl, Kc: int,
+                        tile_begin: int = 0, tile_end: int = None, S: torch.Tensor = None,
+                        tile_chunk: int = 2048) -> torch.Tensor:
+    """int64 [n, Kc] on the device: S[i, c] += sum over j != i with cl[j] == c of C_ij * 2^40
+    (exact integers) for the pairs of tiles [tile_begin, tile_end) (default: all of them), from
+    the label matrix of one K.  cl: int32 [n] (device tensor, or any host int array), an id
+    outside [0, Kc) = no cluster.  S is accumulated into when given (int64 [n, Kc], contiguous),
+    else it starts at zero.  The range is walked `tile_chunk` tiles at a time (cc_cosample, then
+    cc_item_consensus on the current stream), so the scratch is tile_chunk * 128 KiB of
+    co-sampling tiles and no n x n buffer is ever held."""
+    dev = labels_nh.device
+    if tile_end is None:
+        tile_end = num_tiles(n)
+    if tile_chunk < 1:
+        raise ValueError("tile_chunk must be at least 1")
+    if not isinstance(cl, torch.Tensor):
+        cl = torch.from_numpy(np.array(cl, dtype=np.int32))  # a copy: the caller's may be read-only
+    cl = cl.to(device=dev, dtype=torch.int32).contiguous()
+    if cl.numel() != n:
+        raise ValueError(f"cl must hold one cluster id per item ({n}), got {cl.numel()}")
+    if S is None:
+        S = torch.zeros((n, max(int(Kc), 0)), dtype=torch.int64, device=dev)
+    elif (S.dtype != torch.int64 or tuple(S.shape) != (n, Kc) or not S.is_contiguous()
+          or S.device != dev):
+        raise ValueError("S must be a contiguous int64 [n, Kc] tensor on the labels' device")
+    tb = int(tile_begin)
+    while True:
+        te = min(tb + int(tile_chunk), int(tile_end))
+        I_tiles, _ = cosample(labels_nh, n, Hpad, tb, te, want_full=False)
+        with timed("cc_item_consensus"):
+            _lib.call("cc_item_consensus", labels_nh.data_ptr(), n, labels_nh.stride(0), Hpad,
+                      int(K), tb, te, _lib.ptr(I_tiles) or None, cl.data_ptr(), int(Kc),
+                      S.data_ptr() or None, stream_ptr())
+        del I_tiles  # the caching allocator reuses it for the next chunk (same stream)
+        tb = te
+        if tb >= tile_end:
+            break
+    return S
+
+
 def consensus(M: torch.Tensor, I: torch.Tensor) -> torch.Tensor:
     n = M.shape[0]
     C = torch.empty((n, n), dtype=torch.float32, device=M.device)

@@ -161,3 +161,55 @@ def single_linkage_finish(mst, n):
         par[lc] = par[rc] = n + i
         size[n + i] = size[lc] + size[rc]
     return out
+
+
+# ---------------------------------------------------------------- item / cluster consensus
+
+IC_SHIFT = 40  # the device sums hold C_ij * 2^40 (engine.item_consensus_sums)
+
+
+def _cluster_sizes(labels, Kc: int) -> np.ndarray:
+    labels = np.asarray(labels)
+    inside = (labels >= 0) & (labels < Kc)
+    return np.bincount(labels[inside].astype(np.int64), minlength=Kc)[:Kc].astype(np.int64)
+
+
+def item_consensus_from_sums(S, labels, Kc: int) -> np.ndarray:
+    """Monti's item consensus m_i(c) = (1 / (N_c - [i in c])) * sum_{j in c, j != i} C_ij as
+    float64 [n, Kc], from the exact int64 sums S[i, c] = sum C_ij * 2^40: one float64 conversion
+    of S, an exact scaling by 2^-40 and one division.  NaN where the denominator is 0 (an empty
+    cluster, or an item's own singleton cluster).  A label outside [0, Kc) belongs to no cluster."""
+    S = np.asarray(S, dtype=np.int64)
+    labels = np.asarray(labels)
+    n = labels.shape[0]
+    if S.shape != (n, Kc):
+        raise ValueError(f"S must be [n, Kc] = {(n, Kc)}, got {S.shape}")
+    den = np.broadcast_to(_cluster_sizes(labels, Kc), (n, Kc)).astype(np.float64)
+    own = (labels >= 0) & (labels < Kc)
+    den[np.flatnonzero(own), labels[own].astype(np.int64)] -= 1.0
+    out = np.full((n, Kc), np.nan, dtype=np.float64)
+    np.divide(np.ldexp(S.astype(np.float64), -IC_SHIFT), den, out=out, where=den > 0)
+    return out
+
+
+def cluster_consensus_from_sums(S, labels, Kc: int) -> np.ndarray:
+    """Monti's cluster consensus m(c) = (2 / (N_c (N_c - 1))) * sum_{i < j in c} C_ij as float64
+    [Kc]: T_c = sum_{i in c} S[i, c] counts every pair of c twice, so m(c) = T_c 2^-40 /
+    (N_c (N_c - 1)).  T_c is summed exactly in Python integers (it passes int64 from n ~ 3000 in
+    one cluster on), and the quotient of the two integers is rounded once.  NaN when N_c < 2."""
+    S = np.asarray(S, dtype=np.int64)
+    labels = np.asarray(labels)
+    n = labels.shape[0]
+    if S.shape != (n, Kc):
+        raise ValueError(f"S must be [n, Kc] = {(n, Kc)}, got {S.shape}")
+    sizes = _cluster_sizes(labels, Kc)
+    out = np.full(Kc, np.nan, dtype=np.float64)
+    for c in range(Kc):
+        Nc = int(sizes[c])
+        if Nc < 2:
+            continue
+        col = S[labels == c, c]
+        # exact: 32-bit limbs summed in int64 (each below 2^32 * n), joined as Python ints
+        T = (int((col >> 32).sum()) << 32) + int((col & 0xFFFFFFFF).sum())
+        out[c] = T / ((Nc * (Nc - 1)) << IC_SHIFT)  # int / int: correctly rounded
+    return out

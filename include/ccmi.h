@@ -19,6 +19,7 @@
  *   cc_cosample           CC.py:264  I = S^T S            (int8 MFMA, upper-triangle tiles)
  *   cc_coassoc            CC.py:287-290 + :338-344  M += L^T L fused with the 20-bin histogram
  *   cc_consensus          CC.py:372-373  C = f32(M) / f32(I + 1e-6), diag 1
+ *   cc_item_consensus     (no reference code) item / cluster consensus sums of C by cluster
  *   cc_kmeans_plan        packing of the (K, init) problems of one resample into units
  *   cc_split_f16          f16 hi/lo operand image of the rows for the k-means MFMAs
  *   cc_kmeans_batched     CC.py:282 clusterer.fit_predict for every (h, K) at once
@@ -124,6 +125,20 @@ int cc_coassoc(const int8_t* labels_nh, int n, int ldl, int Hpad, int K, int64_t
                int64_t tile_end, const uint16_t* I_tiles, const float* edges,
                unsigned long long* bin_counts, int32_t* M_full, const uint16_t* bin_table,
                int table_rows, void* stream);
+
+/* Item consensus sums (Monti's item / cluster consensus without the n x n matrix):
+ * S[i*Kc + c] += sum over j != i with cl[j] == c of C_ij * 2^40 (exact integers), for the pairs
+ * covered by tiles [tile_begin, tile_end). S is accumulated into: the caller zeroes it.
+ * C_ij = f32(M_ij) / f32(I_ij + 1e-6) as cc_consensus computes it; C_ij * 2^40 is an integer
+ * for Hpad <= 65535, and the int64 sums are exact for n <= 2^22, so disjoint tile ranges (and
+ * ranks) add to the same S in any order.
+ * I_tiles: as written by cc_cosample for the same tile range.
+ * cl: [n] int32 device, the cluster of each item; an id outside [0, Kc) means "no cluster" (the
+ *     item adds to no column, its own row is still filled).  S: [n][Kc] int64 device, 8-B aligned.
+ * K, Kc in [1, 127]. */
+int cc_item_consensus(const int8_t* labels_nh, int n, int ldl, int Hpad, int K,
+                      int64_t tile_begin, int64_t tile_end, const uint16_t* I_tiles,
+                      const int32_t* cl, int Kc, int64_t* S, void* stream);
 
 /* Bin thresholds per co-sampling count i in [0, rows): row i = 21 uint16 T[b] =
  * min{m : bin(f32(m) / f32(i + 1e-6)) >= b} (T[0] = 0, T[20] = 0xFFFF; i + 1 if no m <= i
