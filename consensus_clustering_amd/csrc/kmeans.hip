@@ -23,6 +23,17 @@
 // problems in Lloyd.  Between sweeps the engine retires converged problems, admits new ones
 // and packs the next sweep round-robin, so no slot idles behind a group's slowest init.
 //
+// Shared seeding.  Every fit replays RandomState(seed): the first centre's draw is the same
+// for every K, and the uniforms of init 0 of K' are a prefix of those of any larger K with the
+// same number of local trials t = 2 + floor(ln K) (a TRIAL CLASS).  All problems of a unit see
+// the same rows, and the seeding arithmetic does not depend on K, on the packing or on the wave
+// that runs an item, so init 0 of K' would choose exactly the first K' centres of init 0 of the
+// class's largest K.  Per unit and class that problem (the LEADER, an ordinary problem) seeds
+// alone; the other init-0 problems of the class (FOLLOWERS, ST_FOLLOW) take no seeding slot and
+// no candidate column, and leave for Lloyd after the sweep that gives the leader its centre
+// K' - 1, with the first K' rows of the leader's cpos.  Inits > 0 start at a stream position
+// that depends on K and seed on their own.  CCMI_KM_SHARE_SEED=0 at launch turns the sharing off (A/B runs).
+//
 // Arithmetic.  Rows and centres enter the MFMA as f16 hi/lo pairs of x * 2^s (the exact
 // power-of-two scale keeps the pair inside f16 range): x.c = xh.ch + xh.cl + xl.ch, three
 // v_mfma_f32_32x32x16_f16 per 16 dims with f32 accumulation (22 significant bits per
@@ -131,7 +142,9 @@ __host__ __device__ constexpr int dist_cost() { return KM_COST_DIST_NARROW; }
 
 // Diagnostic build only (-DCC_KM_STAMPS): per-wave cycle accounting of the sweep phases of
 // workgroup 0, added into stats[8 + 8 * wave + k] (k: issue, dist, estep, mstep, commit,
-// barrier) and stats[72..75] (sweep prologue, post-processing, unit setup, output).
+// barrier) and stats[72..75] (sweep prologue, post-processing, unit setup, output); from all
+// workgroups, sweep cycles and counts by width (stats[80..], [96..]) and of the sweeps that
+// carry seeding items (stats[110], [111]).
 #ifdef CC_KM_STAMPS
 #define KM_STAMP(var)                  \
   __builtin_amdgcn_sched_barrier(0);   \
@@ -143,7 +156,9 @@ __host__ __device__ constexpr int dist_cost() { return KM_COST_DIST_NARROW; }
 #define KM_ACC(k, a, b)
 #endif
 
-enum { ST_WAIT = 0, ST_SEED = 1, ST_RUN = 2, ST_FINAL = 3, ST_DONE = 4 };
+// ST_FOLLOW: an init-0 problem that does not seed: it waits for the first K centres of its
+// leader's k-means++ chain (see "Shared seeding" in the header) and then goes to ST_RUN.
+enum { ST_WAIT = 0, ST_SEED = 1, ST_RUN = 2, ST_FINAL = 3, ST_DONE = 4, ST_FOLLOW = 5 };
 enum { IK_SEED0 = 0, IK_SEED = 1, IK_RUN = 2, IK_FINAL = 3 };
 
 struct KArgs {
@@ -178,6 +193,9 @@ struct KArgs {
 // sparse-against-dense parity test.  A device global read once per sweep by the scheduling
 // thread, not a KArgs field: a field moved the sweep loops' register allocation (C3 +0.8 %).
 __device__ int cc_km_dense_only = 0;
+// Diagnostics (CCMI_KM_SHARE_SEED=0 at launch): every problem seeds on its own (no followers),
+// for A/B runs of the shared init-0 seeding in one build.  Read by thread 0 at unit setup.
+__device__ int cc_km_share_seed = 1;
 
 struct State {
   // unit
@@ -216,6 +234,9 @@ struct State {
   int map[KMAX + 1];
   int flag;
   unsigned long long n_lloyd, n_seed, n_mrows, n_reloc, n_sweeps, n_ctiles, n_sparse, n_changes;
+  // shared seeding: the problem whose cpos row holds p's initial centres (p itself unless p is a
+  // follower), and "p leaves ST_FOLLOW after this sweep" (set by schedule())
+  unsigned char lead[PMAX], fgo[PMAX];
 };
 
 // Measured (round 5, C3): the sweep loops ran 7.5 % slower (1653 -> 1775 ms, identical results)
@@ -1140,9 +1161,9 @@ __device__ __forceinline__ void msum_out(const KArgs& a, State& S, float* Sm, co
   if (hh == 0) S.cnt[msl] = tot;
 }
 
-// Thread 0: admit waiting problems into free seeding slots, then pack the next sweep:
-// seeding candidates first (they are on every problem's critical path), then Lloyd
-// problems round-robin from S.rr, first fit into the CW slots.
+// Thread 0: admit waiting problems into free seeding slots (followers, ST_FOLLOW, never
+// seed), then pack the next sweep: seeding candidates first (they are on every problem's
+// critical path), then Lloyd problems round-robin from S.rr, first fit into the CW slots.
 __device__ void schedule(const KArgs& a, State& S, const int32_t* idx, int dist_cost, bool sparse_ok) {
   const int P = S.P;
   for (int p = 0; p < P && S.seedfree; ++p) {
@@ -1184,6 +1205,13 @@ __device__ void schedule(const KArgs& a, State& S, const int32_t* idx, int dist_
       ++nc;
     }
     nseed += static_cast<unsigned long long>(nt) * a.m;
+  }
+  // followers: this sweep gives the leader its centre c; a follower with K = c + 1 then has
+  // all its initial centres and leaves for Lloyd in the post-sweep seeding decision
+  for (int p = 0; p < P; ++p) {
+    const int l = S.lead[p];
+    S.fgo[p] = static_cast<unsigned char>(S.st[p] == ST_FOLLOW && S.st[l] == ST_SEED && S.pitem[l] >= 0 &&
+                                          S.c[l] + 1 == S.K[p]);
   }
   // Lloyd problems: 4-aligned offsets, K padded to a multiple of 4 with dummy (+inf) slots
   int first_skip = -1, last = -1;
@@ -1337,7 +1365,22 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
         S.lcur[p] = 0;
         S.cenoff[p] = static_cast<short>(o);
         o += S.K[p];
+        S.lead[p] = static_cast<unsigned char>(p);
+        S.fgo[p] = 0;
       }
+      // shared seeding: among the unit's init-0 problems with equal ntr (one trial class) the
+      // one with the largest K (the first of them on ties) leads; the others follow it
+      if (cc_km_share_seed)
+        for (int p = 0; p < P; ++p) {
+          if (S.init[p] != 0) continue;
+          int l = p;
+          for (int q = 0; q < P; ++q)
+            if (S.init[q] == 0 && S.ntr[q] == S.ntr[p] && (S.K[q] > S.K[l] || (S.K[q] == S.K[l] && q < l))) l = q;
+          if (l != p) {
+            S.lead[p] = static_cast<unsigned char>(l);
+            S.st[p] = ST_FOLLOW;
+          }
+        }
       S.rr = 0;
       S.seedfree = (a.seedmax >= 32) ? 0xFFFFFFFFu : ((1u << a.seedmax) - 1u);
     }
@@ -1688,7 +1731,7 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
       if (tid < P) {
         const int p = tid;
         S.need_sel[p] = 0;
-        S.to_run[p] = 0;
+        S.to_run[p] = S.fgo[p];  // a follower whose leader's chain reaches its K in this sweep
         if (S.st[p] == ST_SEED && S.pitem[p] >= 0) {
           const int it0 = S.pitem[p], c = S.c[p];
           const int nt = (c == 0) ? 1 : S.ntr[p];
@@ -1718,7 +1761,7 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
       if (tid == 0) {
         for (int p = 0; p < P; ++p)
           if (S.to_run[p]) {
-            S.seedfree |= 1u << S.sslot[p];
+            if (S.st[p] == ST_SEED) S.seedfree |= 1u << S.sslot[p];  // a follower holds none
             S.st[p] = ST_RUN;
             S.iter[p] = 0;
             S.pchg[p] = a.m;
@@ -1738,15 +1781,16 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
           }
         }
       }
-      // initial centres of problems leaving seeding: the chosen rows (exact f32)
+      // initial centres of problems leaving seeding: the chosen rows (exact f32); a follower's
+      // are the first K of its leader's chain
       for (int p = 0; p < P; ++p) {
         if (!S.to_run[p]) continue;
-        const int K = S.K[p];
+        const int K = S.K[p], cp = S.lead[p] * a.Kws;
         for (int e = tid; e < K * DP; e += NT) {
           const int c = e / DP, d = e - c * DP;
-          cen[(S.cenoff[p] + c) * DP + d] = a.X[static_cast<size_t>(idx[cpos[p * a.Kws + c]]) * DP + d];
+          cen[(S.cenoff[p] + c) * DP + d] = a.X[static_cast<size_t>(idx[cpos[cp + c]]) * DP + d];
         }
-        if (tid < K) cenn[S.cenoff[p] + tid] = row_sq(a.X + static_cast<size_t>(idx[cpos[p * a.Kws + tid]]) * DP, a.dreal);
+        if (tid < K) cenn[S.cenoff[p] + tid] = row_sq(a.X + static_cast<size_t>(idx[cpos[cp + tid]]) * DP, a.dreal);
       }
 
       KM_STAMP(ppA);
@@ -1992,6 +2036,10 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
         const int wv = (ncols + 31) / 32;
         atomicAdd(&a.stats[80 + wv], pp1 - swp);
         atomicAdd(&a.stats[96 + wv], 1ull);
+        if (S.ikind[0] < IK_RUN) {  // sweeps that carry seeding items (they are packed first)
+          atomicAdd(&a.stats[110], pp1 - swp);
+          atomicAdd(&a.stats[111], 1ull);
+        }
       }
 #endif
     }
@@ -2308,6 +2356,17 @@ extern "C" int cc_kmeans_batched(const float* X, const uint16_t* Xhl, const floa
         return CC_ERR_HIP;
       }
       dense_set = dense;
+    }
+    static int share_set = 1;
+    const char* sm = std::getenv("CCMI_KM_SHARE_SEED");
+    const int share = (sm && sm[0] == '0') ? 0 : 1;
+    if (share != share_set) {
+      e = hipMemcpyToSymbolAsync(HIP_SYMBOL(cc_km_share_seed), &share, sizeof(int), 0, hipMemcpyHostToDevice, st);
+      if (e != hipSuccess) {
+        cc::set_error(std::string("cc_kmeans_batched: ") + hipGetErrorString(e));
+        return CC_ERR_HIP;
+      }
+      share_set = share;
     }
   }
   const unsigned blocks = static_cast<unsigned>(std::min<long long>(grid, static_cast<long long>(nh) * nU));

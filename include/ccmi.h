@@ -216,6 +216,12 @@ int cc_linkage_check(const void* workspace, size_t ws_bytes, void* stream);
  * grid of workgroups pulls units from an atomic counter and runs each unit's fits as one
  * problem engine (every sweep streams the resample's rows once for up to 256 centroid
  * slots, packed round-robin from the unit's seeding and Lloyd problems).
+ * Within a unit the init-0 problems with the same number of local trials share one
+ * k-means++ chain: every fit replays RandomState(seed), so init 0 of K' chooses exactly the
+ * first K' centres that init 0 of a larger K of that trial class chooses on the same
+ * resample.  Only the largest such K seeds; the others start Lloyd from a prefix of its
+ * centres (results are unchanged; CCMI_KM_SHARE_SEED=0 in the environment at launch makes
+ * every problem seed on its own, for A/B runs).
  * Unit descriptor u (int32, CC_KM_USTRIDE entries): [0] = P (<= CC_KM_PMAX, the n_init
  * runs of one K consecutive), then per problem p: [1+4p] = K, [2+4p] = kidx (index into
  * Ks), [3+4p] = init, [4+4p] = local trials. */

@@ -38,6 +38,8 @@ cnt = st[96:105].astype(float)
 tot = max(cyc.sum(), 1)
 print("sweeps by active waves (1..8): count / share of sweep cycles / mean Mcycles:",
       {w: (int(cnt[w]), f"{100 * cyc[w] / tot:.0f}%", round(cyc[w] / max(cnt[w], 1) / 1e6, 2)) for w in range(1, 9)})
+print("sweeps with seeding items: %d of %d, %.1f%% of the sweep cycles; seeding column-rows %d"
+      % (st[111], st[4], 100 * st[110] / tot, st[1]))
 pp = st[106:110] / 1e6
 print("post-processing phases (wg0, Mcycles): seeding %.1f, label compare %.1f, running sums %.1f, centre update %.1f"
       % tuple(pp))

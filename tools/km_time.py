@@ -39,7 +39,7 @@ for r in range(reps + 1):
     if r:
         ts.append(a.elapsed_time(b))
 print(os.path.basename(os.environ.get("CCMI_LIB", "libccmi.so")), "kmeans ms", [round(t, 1) for t in ts],
-      "sweeps", int(bk.stats[4]), "sparse item-sweeps", int(bk.stats[6]), "changes", int(bk.stats[7]),
+      "sweeps", int(bk.stats[4]), "slot tiles", int(bk.stats[5]), "seeding column-rows", int(bk.stats[1]), "sparse item-sweeps", int(bk.stats[6]), "changes", int(bk.stats[7]),
       "labels sha", hashlib.sha256(L.cpu().numpy().tobytes()).hexdigest()[:16],
       "inertia sha", hashlib.sha256(inert.cpu().numpy().tobytes()).hexdigest()[:16],
       "n_iter sha", hashlib.sha256(nit.cpu().numpy().tobytes()).hexdigest()[:16],
