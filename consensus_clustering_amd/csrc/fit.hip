@@ -22,12 +22,16 @@
 #include <string>
 #include <vector>
 
-#include "ccmi_internal.h"
+#include "kmeans_shared.hpp"
 
 extern "C" int cc_kpp_tables(const int32_t* Ks, int nK, int n_init, uint32_t seed, int m,
                              int weight_f64, double* kpp_u, int kpp_stride, int32_t* kpp_pos);
 
 namespace {
+
+using cc::km::align256;
+using cc::km::hip_status;
+using cc::km::kpp_row_len;
 
 constexpr int RB = 256;  // rows per column-sum block
 
@@ -77,15 +81,6 @@ __global__ void centre_kernel(const float* __restrict__ X, int n, int d, int dpa
   if (threadIdx.x == 0) amax_part[blockIdx.x] = red[0];
 }
 
-int hip_status(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    cc::set_error(std::string(fn) + ": " + hipGetErrorString(e));
-    return CC_ERR_HIP;
-  }
-  return CC_OK;
-}
-
 int dpad_for(int d) {
   for (int p : {32, 64, 128})
     if (d <= p) return p;
@@ -99,15 +94,11 @@ int scale_exponent(float amax) {
   return std::max(-62, std::min(62, e));
 }
 
-size_t align256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
-
 // scratch of cc_prepare_rows: column partials, means, per-block maxima
 size_t prep_scratch_bytes(int n, int d) {
   const size_t nb = (static_cast<size_t>(n) + RB - 1) / RB, nr = (static_cast<size_t>(n) + 255) / 256;
   return align256(nb * d * 8) + align256(static_cast<size_t>(d) * 4) + align256(nr * 4);
 }
-
-int local_trials(int K) { return 2 + static_cast<int>(std::log(static_cast<double>(K))); }
 
 // units per resample: enough to fill every CU of the persistent grid with a balanced last round,
 // as few as possible (kmeans.choose_subsets)
@@ -150,7 +141,7 @@ FitPlan make_plan(int d, int m, int nh, const int32_t* Ks, int nK, int n_init, i
   P.cus = device_cus();
   P.dpad = dpad_for(d);
   int stride = 1;
-  for (int k = 0; k < nK; ++k) stride = std::max(stride, 1 + (Ks[k] - 1) * local_trials(Ks[k]));
+  for (int k = 0; k < nK; ++k) stride = std::max(stride, kpp_row_len(Ks[k]));
   P.stride = stride;
   if (precision == CC_KM_FAST) {
     P.rows_bytes = align256(static_cast<size_t>(n) * P.dpad * 4) + align256(static_cast<size_t>(n) * 4) +

@@ -67,15 +67,11 @@
 #include <string>
 #include <vector>
 
-#include "ccmi_internal.h"
+#include "kmeans_shared.hpp"
 
 namespace {
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef short s4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s4 lds_s4;
+using namespace cc::km;
 
 constexpr int NT = 512;
 constexpr int NW = 8;
@@ -156,10 +152,9 @@ __host__ __device__ constexpr int dist_cost() { return KM_COST_DIST_NARROW; }
 #define KM_ACC(k, a, b)
 #endif
 
-// ST_FOLLOW: an init-0 problem that does not seed: it waits for the first K centres of its
-// leader's k-means++ chain (see "Shared seeding" in the header) and then goes to ST_RUN.
-enum { ST_WAIT = 0, ST_SEED = 1, ST_RUN = 2, ST_FINAL = 3, ST_DONE = 4, ST_FOLLOW = 5 };
-enum { IK_SEED0 = 0, IK_SEED = 1, IK_RUN = 2, IK_FINAL = 3 };
+// Problem states and item kinds: kmeans_shared.hpp.  ST_FOLLOW: an init-0 problem that does not
+// seed: it waits for the first K centres of its leader's k-means++ chain (see "Shared seeding"
+// in the header) and then goes to ST_RUN.
 
 struct KArgs {
   const float* X;          // [n][DP] f32 (mean-centred, zero-padded)
@@ -279,30 +274,6 @@ __device__ __forceinline__ double half_sum(double v) {  // over the 32 lanes of 
   return v;
 }
 
-__device__ __forceinline__ v16f mfma16(const h8& a, const h8& b, const v16f& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-// numpy pairwise_sum of a short contiguous float32 array (n <= 128), as
-// `(center_shift ** 2).sum()` evaluates it (numpy/_core/src/umath/loops_utils.h).
-__device__ __forceinline__ float np_pairwise_sum(const float* a, int n) {
-  if (n < 8) {
-    float res = 0.f;
-    for (int i = 0; i < n; ++i) res += a[i];
-    return res;
-  }
-  float r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = a[j];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-  float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) res += a[i];
-  return res;
-}
-
 // sum of squares of a centre row (sklearn row_norms: f32, sequential).
 __device__ __forceinline__ float row_sq(const float* c, int dreal) {
   float s = 0.f;
@@ -351,21 +322,12 @@ __device__ __forceinline__ void idx_issue(const KArgs& a, const int32_t* idx, in
   I.xsrc = idx[min(r0 + lane, a.m - 1)];
 }
 
-// LDS-DMA piece issued from inline asm: opaque to the compiler's waitcnt pass, which would
-// otherwise put a vmcnt(0) in front of every LDS read it cannot prove disjoint from the DMA
-// (the ds_read_b64_tr_b16 of the M-step), exposing the gather latency mid-iteration.
-// Untracked VMEM ops only make the compiler's own vmcnt waits stricter (the counter drains in
-// order); completion is awaited explicitly by dma_wait() before the barrier that publishes the
-// tile.  M0 is set inside the asm; no compiler-generated code in this kernel uses M0.  No
-// "memory" clobber: the piece writes a ring slot nothing touches until the next barrier and
-// reads immutable rows (a clobber makes the compiler drain vmcnt in front of every piece).
-__device__ __forceinline__ void dma_piece(const void* g, const void* lds_dst, int bytes) {
+// The tile's row norms ride the same way as its 16-B pieces (dma_piece16, kmeans_shared.hpp,
+// whose completion dma_wait() awaits): 4 B per lane.
+__device__ __forceinline__ void dma_piece4(const void* g, const void* lds_dst) {
   const unsigned la = static_cast<unsigned>(reinterpret_cast<uintptr_t>(
       (__attribute__((address_space(3))) const char*)lds_dst));
-  if (bytes == 16)
-    asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(la)), "v"(g));
-  else
-    asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dword %1, off" ::"s"(__builtin_amdgcn_readfirstlane(la)), "v"(g));
+  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dword %1, off" ::"s"(__builtin_amdgcn_readfirstlane(la)), "v"(g));
 }
 
 // DMA source addresses of one tile (computed before anything else is issued, so that the
@@ -411,8 +373,8 @@ __device__ __forceinline__ void tile_issue(const TileAddr<DP>& A, char* slot, fl
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int j = 0; j < GA::PER; ++j)
-    if (wave + NDW * j < GA::NI) dma_piece(A.src[j], slot + 1024 * (wave + NDW * j), 16);  // wave-uniform
-  if (wave == NDW - 1) dma_piece(A.xsrc, xn, 4);
+    if (wave + NDW * j < GA::NI) dma_piece16(A.src[j], slot + 1024 * (wave + NDW * j));  // wave-uniform
+  if (wave == NDW - 1) dma_piece4(A.xsrc, xn);
   __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -476,53 +438,8 @@ __device__ void relocate(const KArgs& a, const int32_t* idx, int p, int off, con
   }
   __syncthreads();
   if (gmax == 0.0) return;  // sklearn returns early when every point sits on its centre
-  const int ne = S.flag;
-  for (int e = 0; e < ne; ++e) {
-    const int c = S.map[e];
-    float bv = -1.f;
-    int bi = 0x7fffffff;
-    for (int r = tid; r < m; r += NT) {
-      const float v = dist[r];
-      if (v > bv) {
-        bv = v;
-        bi = r;
-      }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o);
-      const int oi = __shfl_xor(bi, o);
-      if (ov > bv || (ov == bv && oi < bi)) {
-        bv = ov;
-        bi = oi;
-      }
-    }
-    if ((tid & 63) == 0) {
-      S.red_v[tid >> 6] = bv;
-      S.red_i[tid >> 6] = bi;
-    }
-    __syncthreads();
-    double gv = -2.0;
-    int gi = 0x7fffffff;
-    for (int w = 0; w < NW; ++w)
-      if (S.red_v[w] > gv || (S.red_v[w] == gv && S.red_i[w] < gi)) {
-        gv = S.red_v[w];
-        gi = S.red_i[w];
-      }
-    const int old = glab[gi];
-    const float* x = a.X + static_cast<size_t>(idx[gi]) * DP;
-    for (int d = tid; d < DP; d += NT) {
-      Sm[(off + old) * DP + d] -= x[d];
-      Sm[(off + c) * DP + d] = x[d];
-    }
-    __syncthreads();
-    if (tid == 0) {
-      S.cnt[off + c] = 1;
-      S.cnt[off + old] -= 1;
-      dist[gi] = -1.f;
-      S.n_reloc += 1;
-    }
-    __syncthreads();
-  }
+  relocate_farthest<NT, NW>(m, S.flag, S.map, dist, glab, a.X, idx, DP, off, Sm, S.cnt, S.red_v, S.red_i,
+                            S.n_reloc, tid);
 }
 
 // Wave w's part of the post-sweep label compare of a sparse item: rows [w * seg, (w + 1) * seg)
@@ -659,92 +576,13 @@ __device__ void apply_changes(const KArgs& a, const int32_t* idx, const uint2* l
   }
 }
 
-// k-means++ candidate positions for centre S.c[p] (>= 1) of problem p, one wave:
-// searchsorted(cumsum(closest), u * pot) (side='left': #{cumsum < v}), clipped to m-1.
-// The cumsum is blocked by 32-row tiles: each lane sums whole tiles sequentially in f64 (the
-// in-tile order of the sklearn cumsum), the wave prefix-sums the tile sums, and the crossing
-// tile is walked sequentially from its prefix, so the two levels agree exactly.
+// k-means++ candidate positions for centre S.c[p] (>= 1) of problem p, one wave, from the
+// problem's current closest-distance column (kmeans_shared.hpp).
 template <class St>
 __device__ void kpp_select(const KArgs& a, St& S, int p, const float* closest, int lane) {
-  const int ntr = S.ntr[p], c = S.c[p], m = a.m, T = a.T;
-  const double* u = a.kpp_u + (static_cast<size_t>(S.kidx[p]) * a.n_init + S.init[p]) * a.kpp_stride +
-                    1 + static_cast<size_t>(c - 1) * ntr;
-  const double pot = static_cast<double>(S.pot32[p]);
-  double rv[TMAX], base[TMAX];
-  int tau[TMAX];
-  bool found[TMAX];
-#pragma unroll
-  for (int t = 0; t < TMAX; ++t) {
-    rv[t] = (t < ntr) ? u[t] * pot : 0.0;
-    base[t] = 0.0;
-    tau[t] = T;
-    found[t] = false;
-  }
-  double run = 0.0;
-  for (int b = 0; b < T; b += 64) {
-    const int j = b + lane;
-    double v = 0.0;
-    if (j < T) {
-      const float* rowp = closest + RT * j;
-      const int nr = min(RT, m - RT * j);
-      if (nr == RT) {  // a full tile: all its loads in flight, then the same in-order f64 sum
-        float4 q[RT / 4];
-#pragma unroll
-        for (int r4 = 0; r4 < RT / 4; ++r4) q[r4] = *reinterpret_cast<const float4*>(rowp + 4 * r4);
-#pragma unroll
-        for (int r4 = 0; r4 < RT / 4; ++r4) {
-          v += static_cast<double>(q[r4].x);
-          v += static_cast<double>(q[r4].y);
-          v += static_cast<double>(q[r4].z);
-          v += static_cast<double>(q[r4].w);
-        }
-      } else {
-        for (int r = 0; r < nr; r += 4) {
-          const float4 q = *reinterpret_cast<const float4*>(rowp + r);  // m, RT multiples of 4 or tail
-          v += static_cast<double>(q.x);
-          if (r + 1 < nr) v += static_cast<double>(q.y);
-          if (r + 2 < nr) v += static_cast<double>(q.z);
-          if (r + 3 < nr) v += static_cast<double>(q.w);
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double y = __shfl_up(v, o);
-      if (lane >= o) v += y;
-    }
-    const double cum = run + v;
-    const int nvalid = min(64, T - b);
-#pragma unroll
-    for (int t = 0; t < TMAX; ++t) {
-      if (t >= ntr) continue;
-      const int k = __popcll(__ballot(j < T && cum < rv[t]));
-      const double prev = __shfl(cum, max(k - 1, 0));
-      if (!found[t] && k < nvalid) {
-        found[t] = true;
-        tau[t] = b + k;
-        base[t] = (k == 0) ? run : prev;
-      }
-    }
-    run = __shfl(cum, 63);
-  }
-  // within the crossing tile: lane t walks its rows
-#pragma unroll
-  for (int t = 0; t < TMAX; ++t) {
-    if (t >= ntr || lane != t) continue;
-    int pos = m;
-    if (found[t]) {
-      const int r0 = RT * tau[t];
-      double acc = base[t];
-      int k = 0;
-      for (; k < RT && r0 + k < m; ++k) {
-        acc += static_cast<double>(closest[r0 + k]);
-        if (!(acc < rv[t])) break;
-      }
-      pos = r0 + k;
-    }
-    S.cand[p][t] = min(pos, m - 1);
-  }
+  const int ntr = S.ntr[p];
+  cc::km::kpp_select<RT, TMAX>(closest, a.m, a.T, kpp_uniforms(a.kpp_u, S.kidx[p], a.n_init, S.init[p], a.kpp_stride, S.c[p], ntr),
+                               ntr, static_cast<double>(S.pot32[p]), S.cand[p], lane);
 }
 
 // ---- E-step (all 512 threads): lane = (tile row tid & 31, half-wave hh).  The schedule deals
@@ -775,12 +613,6 @@ constexpr int FLUSH = 32;  // tiles per f32 partial
 // (wave q): in a narrow sweep (one slot tile) the two MFMA blocks use two matrix pipes.
 __host__ __device__ constexpr int mstep_tile(int q) { return (q + 1) % NDW; }
 static_assert(NEW == NDW, "one E/M wave per distance wave");
-
-__device__ __forceinline__ int iw_off(unsigned w) { return w & 0xFF; }
-__device__ __forceinline__ int iw_K(unsigned w) { return (w >> 8) & 0xFF; }
-__device__ __forceinline__ int iw_prob(unsigned w) { return (w >> 16) & 0x3F; }
-__device__ __forceinline__ int iw_kind(unsigned w) { return (w >> 24) & 3; }
-__device__ __forceinline__ int iw_buf(unsigned w) { return (w >> 30) & 1; }
 
 // Seeding step descriptor (one per wave, step and half-wave, every entry initialised; built
 // once per sweep so that a step costs one LDS read instead of three dependent ones, and all
@@ -1733,22 +1565,12 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
         S.need_sel[p] = 0;
         S.to_run[p] = S.fgo[p];  // a follower whose leader's chain reaches its K in this sweep
         if (S.st[p] == ST_SEED && S.pitem[p] >= 0) {
-          const int it0 = S.pitem[p], c = S.c[p];
-          const int nt = (c == 0) ? 1 : S.ntr[p];
-          int best = 0;
-          float bv = static_cast<float>(S.iinert[it0]);
-          for (int t = 1; t < nt; ++t) {
-            const float v = static_cast<float>(S.iinert[it0 + t]);
-            if (v < bv) {
-              bv = v;
-              best = t;
-            }
-          }
-          S.pot32[p] = bv;
-          const int cs = S.cs[p];
-          S.cs[p] = static_cast<unsigned char>((c == 0) ? 0 : ((best < cs) ? best : best + 1));
-          S.sbest[p] = static_cast<unsigned char>(best);
-          cpos[p * a.Kws + c] = (c == 0) ? a.kpp_pos[S.kidx[p] * a.n_init + S.init[p]] : S.cand[p][best];
+          const int c = S.c[p];
+          const KppDecision k = kpp_decide(S.iinert + S.pitem[p], S.ntr[p], c, S.cs[p]);
+          S.pot32[p] = k.pot;
+          S.cs[p] = static_cast<unsigned char>(k.cs);
+          S.sbest[p] = static_cast<unsigned char>(k.best);
+          cpos[p * a.Kws + c] = (c == 0) ? a.kpp_pos[S.kidx[p] * a.n_init + S.init[p]] : S.cand[p][k.best];
           S.c[p] = static_cast<unsigned char>(c + 1);
           if (c + 1 == S.K[p]) {
             S.to_run[p] = 1;  // seeding slot released below (single writer)
@@ -1795,10 +1617,6 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
 
       KM_STAMP(ppA);
       // ---- labels changed? (RUN items): compare this sweep's label buffer with the previous
-      // one, 16 B per thread and load, every item in one pass (flags set by any thread that sees
-      // a difference: one barrier for all items instead of one per item); then this sweep's
-      // buffer becomes the current one
-      // ---- labels changed? (RUN items): compare this sweep's label buffer with the previous
       // one, each wave over its eighth of the rows; the changed rows of a sparse item go to its
       // change list (a dense item's are only counted); then this sweep's buffer becomes the
       // current one
@@ -1827,20 +1645,16 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
             S.ichanged[it] = (tot != 0) | ((S.isparse[it] && over) ? 2u : 0u);  // 2: rebuild the sums
           }
         }
-      } else {  // flags only: 16 B per thread and load, every item in one pass
+      } else {  // flags only, every item in one pass (set by any thread that sees a difference:
+                // one barrier for all items instead of one per item)
         if (tid < nitems) S.ichanged[tid] = 0;
         __syncthreads();
         for (int it = 0; it < nitems; ++it) {
           if (S.ikind[it] != IK_RUN) continue;
           const int p = S.iprob[it];
-          const uint4* cur = reinterpret_cast<const uint4*>(glab + static_cast<size_t>(2 * p + 1 - S.lcur[p]) * a.lsm);
-          const uint4* old = reinterpret_cast<const uint4*>(glab + static_cast<size_t>(2 * p + S.lcur[p]) * a.lsm);
-          bool diff = false;
-          for (int e = tid; e < (m + 15) / 16; e += NT) {
-            const uint4 x = cur[e], y = old[e];
-            diff |= (x.x != y.x) | (x.y != y.y) | (x.z != y.z) | (x.w != y.w);
-          }
-          if (diff) S.ichanged[it] = 1;
+          if (labels_differ<NT>(glab + static_cast<size_t>(2 * p + 1 - S.lcur[p]) * a.lsm,
+                                glab + static_cast<size_t>(2 * p + S.lcur[p]) * a.lsm, m, tid))
+            S.ichanged[it] = 1;
         }
       }
       __syncthreads();
@@ -1989,19 +1803,11 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
       // convergence decisions (_kmeans_single_lloyd :697-736)
       if (tid < nitems && S.ikind[tid] >= IK_RUN) {
         const int it = tid, p = S.iprob[it];
-        if (S.ikind[it] == IK_RUN) {
-          S.iter[p] += 1;
-          if (!S.ichanged[it]) {
-            S.st[p] = ST_DONE;  // strict convergence: final labels are this sweep's
-            S.inert[p] = static_cast<float>(S.iinert[it]);
-          } else {
-            const float tot = np_pairwise_sum(S.shift + S.ioff[it], S.K[p]);
-            S.st[p] = (tot <= S.tol || S.iter[p] >= a.max_iter) ? ST_FINAL : ST_RUN;
-          }
-        } else {
-          S.st[p] = ST_DONE;
-          S.inert[p] = static_cast<float>(S.iinert[it]);
-        }
+        if (S.ikind[it] == IK_RUN) S.iter[p] += 1;
+        const int st = lloyd_next_state(S.ikind[it], S.ichanged[it] != 0, S.shift + S.ioff[it], S.K[p], S.tol,
+                                        a.max_iter, S.iter[p]);
+        S.st[p] = static_cast<unsigned char>(st);
+        if (st == ST_DONE) S.inert[p] = static_cast<float>(S.iinert[it]);  // final labels are this sweep's
       }
       __syncthreads();
       // write back the centres (and norms) of problems that sweep again
@@ -2046,33 +1852,10 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
 
     // ---- best of n_init per K, output (KMeans.fit :1495-1531) -------------------
     for (int p0 = 0; p0 < P; p0 += a.n_init) {
-      int best = p0;
-      for (int i = 1; i < a.n_init; ++i) {
-        const int p = p0 + i;
-        if (!(S.inert[p] < S.inert[best])) continue;
-        // _is_same_clustering(labels_p, labels_best): labels_p -> labels_best must be a function
-        if (tid <= KMAX) S.map[tid] = -1;
-        if (tid == 0) S.flag = 0;
-        __syncthreads();
-        const uint8_t* l1 = glab + static_cast<size_t>(2 * p + S.lcur[p]) * a.lsm;
-        const uint8_t* l2 = glab + static_cast<size_t>(2 * best + S.lcur[best]) * a.lsm;
-        for (int r = tid; r < m; r += NT) S.map[l1[r]] = l2[r];
-        __syncthreads();
-        bool bad = false;
-        for (int r = tid; r < m; r += NT) bad |= (S.map[l1[r]] != l2[r]);
-        if (bad) S.flag = 1;
-        __syncthreads();
-        if (S.flag) best = p;
-        __syncthreads();
-      }
-      const int kidx = S.kidx[p0];
-      const uint8_t* lb = glab + static_cast<size_t>(2 * best + S.lcur[best]) * a.lsm;
-      uint8_t* out = a.labels_out + static_cast<size_t>(kidx) * a.n * a.ldl + h;
-      for (int r = tid; r < m; r += NT) out[static_cast<size_t>(idx[r]) * a.ldl] = lb[r];
-      if (tid == 0) {
-        if (a.inertia_out) a.inertia_out[static_cast<size_t>(kidx) * a.H + h] = S.inert[best];
-        if (a.niter_out) a.niter_out[static_cast<size_t>(kidx) * a.H + h] = S.iter[best];
-      }
+      const auto lab = [&](int p) { return glab + static_cast<size_t>(2 * p + S.lcur[p]) * a.lsm; };
+      const int best = best_of_inits<NT, KMAX>(p0, a.n_init, m, lab, [&](int p) { return S.inert[p]; }, S.map, S.flag, tid);
+      write_fit<NT>(lab(best), idx, m, a.labels_out, a.n, a.ldl, S.kidx[p0], h, a.H, S.inert[best], S.iter[best],
+                    a.inertia_out, a.niter_out, tid);
     }
   }
   if (tid == 0 && a.stats) {
@@ -2100,8 +1883,6 @@ __global__ void split_kernel(const float* X, long long total, int dpad, float sc
   Xhl[row * 2 * dpad + dpad + d] = __builtin_bit_cast(uint16_t, lo);
 }
 
-int local_trials(int K) { return 2 + static_cast<int>(std::log(static_cast<double>(K))); }
-
 struct WsLayout {
   int Pws = 0, Cws = 0, Kws = 0, Tws = 0, lseg = 0;
   size_t off_cen = 0, off_cenn = 0, off_cpos = 0, off_dbuf = 0, off_rdist = 0, off_s64 = 0, off_c64 = 0,
@@ -2128,7 +1909,7 @@ WsLayout ws_layout(int m, int dpad, const int32_t* units, int nU, int seedmax) {
     }
     L.Cws = std::max(L.Cws, cols);
   }
-  auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
+  const auto al = align256;
   L.off_cen = al(static_cast<size_t>(2 * L.Pws) * ((m + 63) & ~63));
   L.off_cenn = L.off_cen + al(static_cast<size_t>(L.Cws) * dpad * sizeof(float));
   L.off_cpos = L.off_cenn + al(static_cast<size_t>(L.Cws) * sizeof(float));
@@ -2229,12 +2010,7 @@ extern "C" int cc_split_f16(const float* X, int n, int dpad, int scale_exp, uint
   const unsigned blocks = static_cast<unsigned>((total + 255) / 256);
   hipLaunchKernelGGL(split_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), X, total,
                      dpad, std::ldexp(1.0f, scale_exp), Xhl);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    cc::set_error(std::string("cc_split_f16: ") + hipGetErrorString(e));
-    return CC_ERR_HIP;
-  }
-  return CC_OK;
+  return hip_status("cc_split_f16");
 }
 
 extern "C" int cc_kmeans_batched(const float* X, const uint16_t* Xhl, const float* xnorm, int n,
@@ -2260,7 +2036,7 @@ extern "C" int cc_kmeans_batched(const float* X, const uint16_t* Xhl, const floa
     cc::set_error("cc_kmeans_batched: dpad must be 32, 64 or 128 (d <= 128 in this build)");
     return CC_ERR_UNSUPPORTED;
   }
-  int kmax = 0, tmax = 0;
+  int kmax = 0;
   for (int g = 0; g < nU; ++g) {
     const int32_t* gd = units_host + static_cast<size_t>(g) * US;
     if (gd[0] <= 0 || gd[0] > PMAX || gd[0] % n_init != 0) {
@@ -2275,10 +2051,9 @@ extern "C" int cc_kmeans_batched(const float* X, const uint16_t* Xhl, const floa
         return CC_ERR_ARG;
       }
       kmax = std::max(kmax, K);
-      tmax = std::max(tmax, gd[4 + 4 * p]);
     }
   }
-  if (kpp_stride < 1 + (kmax - 1) * tmax) {
+  if (kpp_stride < kpp_row_len(kmax)) {
     cc::set_error("cc_kmeans_batched: kpp_stride too small");
     return CC_ERR_ARG;
   }
@@ -2295,10 +2070,7 @@ extern "C" int cc_kmeans_batched(const float* X, const uint16_t* Xhl, const floa
   }
   const hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e = hipMemsetAsync(workspace, 0, sizeof(unsigned), st);
-  if (e != hipSuccess) {
-    cc::set_error(std::string("cc_kmeans_batched: ") + hipGetErrorString(e));
-    return CC_ERR_HIP;
-  }
+  if (e != hipSuccess) return hip_fail("cc_kmeans_batched", e);
   KArgs a{};
   a.X = X;
   a.Xhl = Xhl;
@@ -2351,10 +2123,7 @@ extern "C" int cc_kmeans_batched(const float* X, const uint16_t* Xhl, const floa
     const int dense = (dm && dm[0] == '1') ? 1 : 0;
     if (dense != dense_set) {
       e = hipMemcpyToSymbolAsync(HIP_SYMBOL(cc_km_dense_only), &dense, sizeof(int), 0, hipMemcpyHostToDevice, st);
-      if (e != hipSuccess) {
-        cc::set_error(std::string("cc_kmeans_batched: ") + hipGetErrorString(e));
-        return CC_ERR_HIP;
-      }
+      if (e != hipSuccess) return hip_fail("cc_kmeans_batched", e);
       dense_set = dense;
     }
     static int share_set = 1;
@@ -2362,10 +2131,7 @@ extern "C" int cc_kmeans_batched(const float* X, const uint16_t* Xhl, const floa
     const int share = (sm && sm[0] == '0') ? 0 : 1;
     if (share != share_set) {
       e = hipMemcpyToSymbolAsync(HIP_SYMBOL(cc_km_share_seed), &share, sizeof(int), 0, hipMemcpyHostToDevice, st);
-      if (e != hipSuccess) {
-        cc::set_error(std::string("cc_kmeans_batched: ") + hipGetErrorString(e));
-        return CC_ERR_HIP;
-      }
+      if (e != hipSuccess) return hip_fail("cc_kmeans_batched", e);
       share_set = share;
     }
   }
@@ -2375,10 +2141,5 @@ extern "C" int cc_kmeans_batched(const float* X, const uint16_t* Xhl, const floa
     case 64: launch<64>(a, blocks, st); break;
     default: launch<128>(a, blocks, st); break;
   }
-  e = hipGetLastError();
-  if (e != hipSuccess) {
-    cc::set_error(std::string("cc_kmeans_batched: ") + hipGetErrorString(e));
-    return CC_ERR_HIP;
-  }
-  return CC_OK;
+  return hip_status("cc_kmeans_batched");
 }

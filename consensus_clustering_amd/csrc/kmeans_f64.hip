@@ -54,7 +54,7 @@
 #include <string>
 #include <type_traits>
 
-#include "ccmi_internal.h"
+#include "kmeans_shared.hpp"
 
 #pragma clang fp contract(off)
 
@@ -101,24 +101,10 @@ struct F64Args {
 };
 
 // numpy pairwise_sum (numpy/_core/src/umath/loops_utils.h.src) of a contiguous double array:
-// sequential below 8, eight interleaved partial sums up to 128, else split at
-// floor(n / 2) rounded down to a multiple of 8 and recurse.
+// the leaf of kmeans_shared.hpp up to 128, else split at floor(n / 2) rounded down to a multiple
+// of 8 and recurse.
 __device__ double np_pairwise(const double* a, int n) {
-  if (n < 8) {
-    double r = 0.0;
-    for (int i = 0; i < n; ++i) r += a[i];
-    return r;
-  }
-  if (n <= 128) {
-    double r[8];
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8)
-      for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-  }
+  if (n <= 128) return cc::km::np_pairwise_leaf(a, n);
   int n2 = n / 2;
   n2 -= n2 % 8;
   return np_pairwise(a, n2) + np_pairwise(a + n2, n - n2);
@@ -1386,7 +1372,7 @@ struct F64Layout {
 };
 
 F64Layout f64_layout(int m, int d, int kmax) {
-  auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
+  const auto al = cc::km::align256;
   F64Layout L{};
   size_t o = 0;
   L.o_cl = o;    o += al(sizeof(double) * m * GMAX);
@@ -1460,16 +1446,15 @@ extern "C" int cc_kmeans_f64(const double* X, int n, int d, const int32_t* idx_h
     cc::set_error("cc_kmeans_f64: X must be 8-B and the workspace 16-B aligned");
     return CC_ERR_ARG;
   }
-  int kmax = 1, tmax = 0;
+  int kmax = 1;
   for (int i = 0; i < nK; ++i) {
     if (Ks[i] < 1 || Ks[i] > KMAX || Ks[i] > m) {
       cc::set_error("cc_kmeans_f64: need 1 <= K <= min(127, m)");
       return CC_ERR_ARG;
     }
     kmax = std::max(kmax, Ks[i]);
-    tmax = std::max(tmax, 2 + static_cast<int>(std::log(static_cast<double>(Ks[i]))));
   }
-  if (kpp_stride < 1 + (kmax - 1) * tmax) {
+  if (kpp_stride < cc::km::kpp_row_len(kmax)) {
     cc::set_error("cc_kmeans_f64: kpp_stride too small");
     return CC_ERR_ARG;
   }
@@ -1594,10 +1579,7 @@ extern "C" int cc_kmeans_f64(const double* X, int n, int d, const int32_t* idx_h
       else hipLaunchKernelGGL(kmeans_f64_kernel<4>, dim3(blocks), dim3(NT), 0, st, pa);
       e = hipGetLastError();
     }
-    if (e != hipSuccess) {
-      cc::set_error(std::string("cc_kmeans_f64: ") + hipGetErrorString(e));
-      return CC_ERR_HIP;
-    }
+    if (e != hipSuccess) return cc::km::hip_fail("cc_kmeans_f64", e);
   }
   return CC_OK;
 }

@@ -32,15 +32,11 @@
 #include <string>
 #include <vector>
 
-#include "ccmi_internal.h"
+#include "kmeans_shared.hpp"
 
 namespace {
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef short s4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s4 lds_s4;
+using namespace cc::km;
 
 constexpr int NT = 512;
 constexpr int NW = 8;
@@ -62,16 +58,8 @@ constexpr int RTB = 32;          // k-means++ cumsum block (rows)
 #define KW_ALIGN 1               // align the problems' Lloyd phases (schedule)
 #endif
 
-enum { ST_SEED = 1, ST_RUN = 2, ST_FINAL = 3, ST_DONE = 4 };
-enum { IK_SEED0 = 0, IK_SEED = 1, IK_RUN = 2, IK_FINAL = 3 };
-
-// Item words: iw0 = label buffer<<30 | kind<<24 | problem<<16 | K<<8 | slot offset,
-//             iw1 = dbuf write slot<<8 | closest slot<<4 | trial (seeding items).
-__device__ __forceinline__ int iw_off(unsigned w) { return w & 0xFF; }
-__device__ __forceinline__ int iw_K(unsigned w) { return (w >> 8) & 0xFF; }
-__device__ __forceinline__ int iw_prob(unsigned w) { return (w >> 16) & 0x3F; }
-__device__ __forceinline__ int iw_kind(unsigned w) { return (w >> 24) & 3; }
-__device__ __forceinline__ int iw_buf(unsigned w) { return (w >> 30) & 1; }
+// Problem states, item kinds and item word 0: kmeans_shared.hpp.
+// Item word 1 = dbuf write slot<<8 | closest slot<<4 | trial (seeding items).
 
 // One column tile of a round (global; written by P, read by E and M of the next round).
 struct WTile {
@@ -155,10 +143,6 @@ __device__ __forceinline__ RP rp(const WArgs& a, int b) {
   return r;
 }
 
-__device__ __forceinline__ v16f mfma16(const h8& a, const h8& b, const v16f& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -173,34 +157,7 @@ __device__ __forceinline__ void amin4(const float4& v, int c, float& best, int& 
   if (v.w < best) { best = v.w; lab = c + 3; }
 }
 
-// numpy pairwise_sum of a short float32 array (n <= 128): `(center_shift ** 2).sum()`.
-__device__ __forceinline__ float np_pairwise_sum(const float* a, int n) {
-  if (n < 8) {
-    float res = 0.f;
-    for (int i = 0; i < n; ++i) res += a[i];
-    return res;
-  }
-  float r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = a[j];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-  float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) res += a[i];
-  return res;
-}
-
-// LDS-DMA piece from inline asm (lane i writes 16 B at M0 + 16 i), opaque to the compiler's
-// waitcnt pass; completion is awaited explicitly with dma_wait_n (vmcnt drains in order).  M0
-// is set inside the asm; nothing else in these kernels uses M0.
-__device__ __forceinline__ void dma_piece16(const void* g, const void* lds_dst) {
-  const unsigned la = static_cast<unsigned>(reinterpret_cast<uintptr_t>(
-      (__attribute__((address_space(3))) const char*)lds_dst));
-  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(la)), "v"(g));
-}
-
+// Awaits the LDS-DMA pieces (dma_piece16, kmeans_shared.hpp): vmcnt drains in order.
 template <int N>
 __device__ __forceinline__ void dma_wait_n() {
   if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -669,72 +626,6 @@ struct PS {
   WTile tn[CTMAX];
 };
 
-// k-means++ candidate positions for centre c (>= 1) of problem p, one wave:
-// searchsorted(cumsum(closest), u * pot) (side='left'), clipped to m-1.  The cumsum is blocked
-// by 32-row blocks (f64 block sums in row order, a wave prefix over blocks, then a walk of the
-// crossing block), so the two levels agree exactly.
-__device__ void kpp_select(const WArgs& a, WProb& q, const float* closest, int lane) {
-  const int ntr = q.ntr, c = q.c, m = a.m, T = (m + RTB - 1) / RTB;
-  const double* u = a.kpp_u + (static_cast<size_t>(q.kidx) * a.n_init + q.init) * a.kpp_stride + 1 +
-                    static_cast<size_t>(c - 1) * ntr;
-  const double pot = static_cast<double>(q.pot32);
-  double rv[TMAX], base[TMAX];
-  int tau[TMAX];
-  bool found[TMAX];
-#pragma unroll
-  for (int t = 0; t < TMAX; ++t) {
-    rv[t] = (t < ntr) ? u[t] * pot : 0.0;
-    base[t] = 0.0;
-    tau[t] = T;
-    found[t] = false;
-  }
-  double run = 0.0;
-  for (int b0 = 0; b0 < T; b0 += 64) {
-    const int j = b0 + lane;
-    double v = 0.0;
-    if (j < T) {
-      const int r0 = RTB * j, nr = min(RTB, m - r0);
-      for (int k = 0; k < nr; ++k) v += static_cast<double>(closest[r0 + k]);
-    }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double y = __shfl_up(v, o);
-      if (lane >= o) v += y;
-    }
-    const double cum = run + v;
-    const int nvalid = min(64, T - b0);
-#pragma unroll
-    for (int t = 0; t < TMAX; ++t) {
-      if (t >= ntr) continue;
-      const int k = __popcll(__ballot(j < T && cum < rv[t]));
-      const double prev = __shfl(cum, max(k - 1, 0));
-      if (!found[t] && k < nvalid) {
-        found[t] = true;
-        tau[t] = b0 + k;
-        base[t] = (k == 0) ? run : prev;
-      }
-    }
-    run = __shfl(cum, 63);
-  }
-#pragma unroll
-  for (int t = 0; t < TMAX; ++t) {
-    if (t >= ntr || lane != t) continue;
-    int pos = m;
-    if (found[t]) {
-      const int r0 = RTB * tau[t];
-      double acc = base[t];
-      int k = 0;
-      for (; k < RTB && r0 + k < m; ++k) {
-        acc += static_cast<double>(closest[r0 + k]);
-        if (!(acc < rv[t])) break;
-      }
-      pos = r0 + k;
-    }
-    q.cand[t] = min(pos, m - 1);
-  }
-}
-
-
 // One new centre row (one wave): nw <- nw * alpha (the f32 _average_centers scaling, in
 // place), shift = |nw - od|^2 (f64 sum -> f32, squared back from its f32 root as
 // _euclidean_dense_dense + `** 2`), the f16 hi/lo image and the f32 squared norm.  Four 16-B
@@ -790,7 +681,7 @@ __device__ void update_row(const WArgs& a, float* nw, const float* od, float alp
 }
 
 // Empty-cluster relocation for problem p (rare; _k_means_common.pyx:167-212).  sums: the
-// problem's un-averaged sums [K][dpad]; cold: the centres the labels came from; est: the E-step's
+// resample's un-averaged sums [Cn][dpad] (the problem's rows start at its cenoff); cold: the centres the labels came from; est: the E-step's
 // squared distance of each row to its centre, cn: the squared norms of cold.
 //
 // The clusters take the farthest rows by the exact distance (f64 sum of the f32 squared
@@ -827,26 +718,9 @@ __device__ void relocate(const WArgs& a, PS& L, const int32_t* idx, int p, float
         bi = r;
       }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o);
-      const int oi = __shfl_xor(bi, o);
-      if (ov > bv || (ov == bv && oi < bi)) {
-        bv = ov;
-        bi = oi;
-      }
-    }
-    if (lane == 0) {
-      L.red_v[wave] = bv;
-      L.red_i[wave] = bi;
-    }
-    __syncthreads();
-    double gv = -__builtin_huge_val();
-    int gi = 0x7fffffff;
-    for (int w = 0; w < NW; ++w)
-      if (L.red_v[w] > gv || (L.red_v[w] == gv && L.red_i[w] < gi)) {
-        gv = L.red_v[w];
-        gi = L.red_i[w];
-      }
+    double gv;
+    int gi;
+    wg_argmax_lowest<NW>(bv, bi, L.red_v, L.red_i, tid, gv, gi);
     __syncthreads();
     pv = static_cast<float>(gv);
     pi = gi;
@@ -886,53 +760,8 @@ __device__ void relocate(const WArgs& a, PS& L, const int32_t* idx, int p, float
   }
   __syncthreads();
   if (gmax == 0.0) return;
-  const int ne = L.flag;
-  for (int e = 0; e < ne; ++e) {
-    const int c = L.map[e];
-    float bv = -1.f;
-    int bi = 0x7fffffff;
-    for (int r = tid; r < m; r += NT) {
-      const float v = dist[r];
-      if (v > bv) {
-        bv = v;
-        bi = r;
-      }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o);
-      const int oi = __shfl_xor(bi, o);
-      if (ov > bv || (ov == bv && oi < bi)) {
-        bv = ov;
-        bi = oi;
-      }
-    }
-    if ((tid & 63) == 0) {
-      L.red_v[tid >> 6] = bv;
-      L.red_i[tid >> 6] = bi;
-    }
-    __syncthreads();
-    double gv = -2.0;
-    int gi = 0x7fffffff;
-    for (int w = 0; w < NW; ++w)
-      if (L.red_v[w] > gv || (L.red_v[w] == gv && L.red_i[w] < gi)) {
-        gv = L.red_v[w];
-        gi = L.red_i[w];
-      }
-    const int old = lab[gi];
-    const float* x = a.X + static_cast<size_t>(idx[gi]) * dpad;
-    for (int d = tid; d < dpad; d += NT) {
-      sums[static_cast<size_t>(old) * dpad + d] -= x[d];
-      sums[static_cast<size_t>(c) * dpad + d] = x[d];
-    }
-    __syncthreads();
-    if (tid == 0) {
-      L.cnt[off + c] = 1;
-      L.cnt[off + old] -= 1;
-      dist[gi] = -1.f;
-      L.n_reloc += 1;
-    }
-    __syncthreads();
-  }
+  relocate_farthest<NT, NW>(m, L.flag, L.map, dist, lab, a.X, idx, dpad, off, sums, L.cnt, L.red_v, L.red_i,
+                            L.n_reloc, tid);
 }
 
 // Thread 0: pack the next round.  Lloyd problems first (4-aligned offsets, K padded to a
@@ -1095,21 +924,11 @@ __device__ void post_body(const WArgs& a, PS& L, bool init) {
       q.need_sel = 0;
       q.to_run = 0;
       if (q.st == ST_SEED && q.item >= 0) {
-        const int fi0 = q.item, c = q.c;
-        const int nt = (c == 0) ? 1 : q.ntr;
-        int best = 0;
-        float bv = static_cast<float>(L.iinert[fi0]);
-        for (int t = 1; t < nt; ++t) {
-          const float v = static_cast<float>(L.iinert[fi0 + t]);
-          if (v < bv) {
-            bv = v;
-            best = t;
-          }
-        }
-        q.pot32 = bv;
-        const int cs = q.cs;
-        q.cs = static_cast<unsigned char>((c == 0) ? 0 : ((best < cs) ? best : best + 1));
-        R.cpos[tid * a.kws + c] = (c == 0) ? a.kpp_pos[q.kidx * a.n_init + q.init] : q.cand[best];
+        const int c = q.c;
+        const KppDecision k = kpp_decide(L.iinert + q.item, q.ntr, c, q.cs);
+        q.pot32 = k.pot;
+        q.cs = static_cast<unsigned char>(k.cs);
+        R.cpos[tid * a.kws + c] = (c == 0) ? a.kpp_pos[q.kidx * a.n_init + q.init] : q.cand[k.best];
         q.c = static_cast<unsigned char>(c + 1);
         if (c + 1 == q.K) {
           q.to_run = 1;
@@ -1127,7 +946,10 @@ __device__ void post_body(const WArgs& a, PS& L, bool init) {
         if (!S.pr[p].need_sel) continue;
         if ((j++ % NW) != wave) continue;
         WProb& q = S.pr[p];
-        kpp_select(a, q, R.dbuf + (static_cast<size_t>(p) * a.ndb + q.cs) * a.lsm, lane);
+        // the column is 16-B aligned: the workspace, ws_per and off_dbuf are, and lsm is a multiple of 64
+        kpp_select<RTB, TMAX>(R.dbuf + (static_cast<size_t>(p) * a.ndb + q.cs) * a.lsm, m, (m + RTB - 1) / RTB,
+                              kpp_uniforms(a.kpp_u, q.kidx, a.n_init, q.init, a.kpp_stride, q.c, q.ntr), q.ntr,
+                              static_cast<double>(q.pot32), q.cand, lane);
       }
     }
     // initial centres of problems leaving seeding: the chosen rows (exact f32), their f16 image
@@ -1154,15 +976,9 @@ __device__ void post_body(const WArgs& a, PS& L, bool init) {
       WProb& q = S.pr[p];
       if (q.item < 0 || (q.st != ST_RUN && q.st != ST_FINAL) || q.to_run) continue;
       const unsigned w0 = L.iw0[q.item / IMW][q.item % IMW];
-      bool diff = false;
-      if (iw_kind(w0) == IK_RUN) {
-        const uint4* cur = reinterpret_cast<const uint4*>(R.glab + (static_cast<size_t>(p) * 2 + 1 - q.lcur) * a.lsm);
-        const uint4* old = reinterpret_cast<const uint4*>(R.glab + (static_cast<size_t>(p) * 2 + q.lcur) * a.lsm);
-        for (int e = tid; e < (m + 15) / 16; e += NT) {
-          const uint4 x = cur[e], y = old[e];
-          diff |= (x.x != y.x) | (x.y != y.y) | (x.z != y.z) | (x.w != y.w);
-        }
-      }
+      const bool diff = iw_kind(w0) == IK_RUN &&
+                        labels_differ<NT>(R.glab + (static_cast<size_t>(p) * 2 + 1 - q.lcur) * a.lsm,
+                                          R.glab + (static_cast<size_t>(p) * 2 + q.lcur) * a.lsm, m, tid);
       const int any = __syncthreads_or(diff);
       if (tid == 0) {
         q.changed = any != 0;
@@ -1203,7 +1019,7 @@ __device__ void post_body(const WArgs& a, PS& L, bool init) {
       for (int p = 0; p < P; ++p) {
         if (!ran(p) || S.pr[p].nempty == 0) continue;
         const WProb& q = S.pr[p];
-        relocate(a, L, idx, p, R.cen + (static_cast<size_t>(1 - q.ccur) * Cn + q.cenoff) * dpad,
+        relocate(a, L, idx, p, R.cen + static_cast<size_t>(1 - q.ccur) * Cn * dpad,
                  R.cen + (static_cast<size_t>(q.ccur) * Cn + q.cenoff) * dpad,
                  R.glab + (static_cast<size_t>(p) * 2 + q.lcur) * a.lsm,
                  R.dbuf + static_cast<size_t>(p) * a.ndb * a.lsm, R.cenn + q.cenoff, R.rdist, tid);
@@ -1278,21 +1094,11 @@ __device__ void post_body(const WArgs& a, PS& L, bool init) {
       WProb& q = S.pr[tid];
       if (q.item >= 0 && !q.to_run && (q.st == ST_RUN || q.st == ST_FINAL)) {
         const int kind = iw_kind(L.iw0[q.item / IMW][q.item % IMW]);
-        const float inert = static_cast<float>(L.iinert[q.item]);
-        if (kind == IK_RUN) {
-          q.iter += 1;
-          if (!q.changed) {
-            q.st = ST_DONE;  // strict convergence: the final labels are this round's
-            q.inert = inert;
-          } else {
-            const float tot = np_pairwise_sum(L.shift + q.cenoff, q.K);
-            q.st = (tot <= S.tol || q.iter >= a.max_iter) ? ST_FINAL : ST_RUN;
-            q.ccur = static_cast<unsigned char>(1 - q.ccur);  // the averaged sums are the centres now
-          }
-        } else {
-          q.st = ST_DONE;
-          q.inert = inert;
-        }
+        if (kind == IK_RUN) q.iter += 1;
+        const int st = lloyd_next_state(kind, q.changed != 0, L.shift + q.cenoff, q.K, S.tol, a.max_iter, q.iter);
+        q.st = static_cast<unsigned char>(st);
+        if (st == ST_DONE) q.inert = static_cast<float>(L.iinert[q.item]);  // the final labels are this round's
+        else q.ccur = static_cast<unsigned char>(1 - q.ccur);               // the averaged sums are the centres now
       }
     }
     __syncthreads();
@@ -1301,33 +1107,11 @@ __device__ void post_body(const WArgs& a, PS& L, bool init) {
     for (int p = 0; p < P; ++p) all_done &= (S.pr[p].st == ST_DONE);
     if (all_done) {
       for (int p0 = 0; p0 < P; p0 += a.n_init) {
-        int best = p0;
-        for (int i = 1; i < a.n_init; ++i) {
-          const int p = p0 + i;
-          if (!(S.pr[p].inert < S.pr[best].inert)) continue;
-          // _is_same_clustering(labels_p, labels_best): labels_p -> labels_best must be a function
-          if (tid <= KMAX) L.map[tid] = -1;
-          if (tid == 0) L.flag = 0;
-          __syncthreads();
-          const uint8_t* l1 = R.glab + (static_cast<size_t>(p) * 2 + S.pr[p].lcur) * a.lsm;
-          const uint8_t* l2 = R.glab + (static_cast<size_t>(best) * 2 + S.pr[best].lcur) * a.lsm;
-          for (int r = tid; r < m; r += NT) L.map[l1[r]] = l2[r];
-          __syncthreads();
-          bool bad = false;
-          for (int r = tid; r < m; r += NT) bad |= (L.map[l1[r]] != l2[r]);
-          if (bad) L.flag = 1;
-          __syncthreads();
-          if (L.flag) best = p;
-          __syncthreads();
-        }
-        const int kidx = S.pr[p0].kidx;
-        const uint8_t* lb = R.glab + (static_cast<size_t>(best) * 2 + S.pr[best].lcur) * a.lsm;
-        uint8_t* out = a.labels_out + static_cast<size_t>(kidx) * a.n * a.ldl + h;
-        for (int r = tid; r < m; r += NT) out[static_cast<size_t>(idx[r]) * a.ldl] = lb[r];
-        if (tid == 0) {
-          if (a.inertia_out) a.inertia_out[static_cast<size_t>(kidx) * a.H + h] = S.pr[best].inert;
-          if (a.niter_out) a.niter_out[static_cast<size_t>(kidx) * a.H + h] = S.pr[best].iter;
-        }
+        const auto lab = [&](int p) { return R.glab + (static_cast<size_t>(p) * 2 + S.pr[p].lcur) * a.lsm; };
+        const int best =
+            best_of_inits<NT, KMAX>(p0, a.n_init, m, lab, [&](int p) { return S.pr[p].inert; }, L.map, L.flag, tid);
+        write_fit<NT>(lab(best), idx, m, a.labels_out, a.n, a.ldl, S.pr[p0].kidx, h, a.H, S.pr[best].inert,
+                      S.pr[best].iter, a.inertia_out, a.niter_out, tid);
       }
       if (tid == 0) S.finished = 1;
     }
@@ -1375,8 +1159,6 @@ __global__ __launch_bounds__(NT, 1) void wide_post(WArgs a) {
   post_body(a, L, false);
 }
 
-int local_trials(int K) { return 2 + static_cast<int>(std::log(static_cast<double>(K))); }
-
 constexpr size_t HDR = 4096;  // active counter + problem table
 
 struct WL {
@@ -1417,7 +1199,7 @@ bool wide_layout(int m, int dpad, const int32_t* Ks, int nK, int n_init, WL& L) 
   L.RE = (m + ER - 1) / ER;
   L.DT = (dpad + MDW - 1) / MDW;
   L.lsm = (m + 63) & ~63;
-  auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
+  const auto al = align256;
   size_t o = al(sizeof(WState));
   L.off_tolp = o;
   o += al(sizeof(double) * ((dpad + NT - 1) / NT));
@@ -1441,11 +1223,6 @@ bool wide_layout(int m, int dpad, const int32_t* Ks, int nK, int n_init, WL& L) 
   o += al(sizeof(float) * L.lsm);
   L.per = o;
   return true;
-}
-
-int hip_fail(const char* what, hipError_t e) {
-  cc::set_error(std::string("cc_kmeans_wide: ") + what + ": " + hipGetErrorString(e));
-  return CC_ERR_HIP;
 }
 
 }  // namespace
@@ -1477,12 +1254,7 @@ extern "C" int cc_kmeans_wide(const float* X, const uint16_t* Xhl, const float* 
   }
   WL L;
   if (!wide_layout(m, dpad, Ks, nK, n_init, L)) return CC_ERR_UNSUPPORTED;
-  int kmax = 0, tmax = 0;
-  for (int k = 0; k < nK; ++k) {
-    kmax = std::max(kmax, Ks[k]);
-    tmax = std::max(tmax, local_trials(Ks[k]));
-  }
-  if (kpp_stride < 1 + (kmax - 1) * tmax) {
+  if (kpp_stride < kpp_row_len(*std::max_element(Ks, Ks + nK))) {
     cc::set_error("cc_kmeans_wide: kpp_stride too small");
     return CC_ERR_ARG;
   }
@@ -1507,7 +1279,7 @@ extern "C" int cc_kmeans_wide(const float* X, const uint16_t* Xhl, const float* 
   int* active = reinterpret_cast<int*>(base);
   int32_t* probs_d = reinterpret_cast<int32_t*>(base + 256);
   hipError_t e = hipMemcpyAsync(probs_d, probs.data(), probs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return hip_fail("problem table", e);
+  if (e != hipSuccess) return hip_fail("cc_kmeans_wide: problem table", e);
 
   WArgs a{};
   a.X = X;
@@ -1563,18 +1335,18 @@ extern "C" int cc_kmeans_wide(const float* X, const uint16_t* Xhl, const float* 
     const int nb = std::min(batch, h_end - h0);
     a.h0 = h0;
     a.nb = nb;
-    if ((e = hipMemsetAsync(active, 0, sizeof(int), st)) != hipSuccess) return hip_fail("memset", e);
+    if ((e = hipMemsetAsync(active, 0, sizeof(int), st)) != hipSuccess) return hip_fail("cc_kmeans_wide: memset", e);
     hipLaunchKernelGGL(wide_tol, dim3(nb * ((dreal + NT - 1) / NT)), dim3(NT), 0, st, a);
     hipLaunchKernelGGL(wide_init, dim3(nb), dim3(NT), 0, st, a);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail("init launch", e);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail("cc_kmeans_wide: init launch", e);
     const int G = nb * L.nct;
     const unsigned eblocks = static_cast<unsigned>(8 * ((L.RE + 1) / 2) * ((G + 7) / 8));  // 256-row E tiles
     const unsigned mblocks = static_cast<unsigned>(G * L.DT);
     for (long long round = 0;; ++round) {
       int act = 0;
       if ((e = hipMemcpyAsync(&act, active, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess)
-        return hip_fail("active count", e);
-      if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail("round sync", e);
+        return hip_fail("cc_kmeans_wide: active count", e);
+      if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail("cc_kmeans_wide: round sync", e);
       if (act == 0) break;
       if (round >= round_cap) {
         cc::set_error("cc_kmeans_wide: round cap exceeded");
@@ -1582,9 +1354,9 @@ extern "C" int cc_kmeans_wide(const float* X, const uint16_t* Xhl, const float* 
       }
       hipLaunchKernelGGL(wide_estep, dim3(eblocks), dim3(NT), 0, st, a);
       hipLaunchKernelGGL(wide_mstep, dim3(mblocks), dim3(NT), 0, st, a);
-      if ((e = hipMemsetAsync(active, 0, sizeof(int), st)) != hipSuccess) return hip_fail("memset", e);
+      if ((e = hipMemsetAsync(active, 0, sizeof(int), st)) != hipSuccess) return hip_fail("cc_kmeans_wide: memset", e);
       hipLaunchKernelGGL(wide_post, dim3(nb), dim3(NT), 0, st, a);
-      if ((e = hipGetLastError()) != hipSuccess) return hip_fail("round launch", e);
+      if ((e = hipGetLastError()) != hipSuccess) return hip_fail("cc_kmeans_wide: round launch", e);
     }
   }
   return CC_OK;

@@ -38,7 +38,7 @@ def test_bench_json_contract_c2():
     assert len(d["step_ms"]) == steps == len(d["fit_total_ms"])
     for wall, fit in zip(d["step_ms"], d["fit_total_ms"]):
         assert abs(wall - fit) < 5.0, (d["step_ms"], d["fit_total_ms"])
-    assert sum(d["step_ms"]) <= steps * d["ms_per_step"] + 1e-6
+    assert sum(d["step_ms"]) <= steps * d["ms_per_step"] + 0.05 * steps + 1e-6  # step_ms: rounded to 0.1 ms
 
     r = d["roofline"]
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
@@ -76,9 +76,10 @@ def test_bench_plain_run_and_dump_outputs(tmp_path):
         assert k in d, k
     assert "cpu_baseline" not in d and "roofline_consensus" not in d
     assert d["steps"] == steps == len(d["step_ms"])
-    assert sum(d["step_ms"]) <= steps * d["ms_per_step"] + 1e-6
+    # the steps lie inside the timed region; step_ms is rounded to 0.1 ms per step, ms_per_step is not
+    assert sum(d["step_ms"]) <= steps * d["ms_per_step"] + 0.05 * steps + 1e-6
 
-    files = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    files ={p.stem: np.load(p) for p in out.glob("*.npy")}
     assert {"K_range", "hist", "cdf", "bin_edges", "pac_area", "cdf_area", "delta_k", "best_k", "pair_counts",
             "kmeans_inertia", "kmeans_n_iter", "label_rows", "labels"} <= set(files)
     assert all(a.dtype in (np.float32, np.float64) for a in files.values())

@@ -427,6 +427,60 @@ def test_f64_relocation_with_ties_is_pinned():
           f"tie rule; numpy's tie order changes sklearn's labels in {differs_from_numpy} of them")
 
 
+# d -> seeds of _narrow_reloc_case whose sklearn float32 fit relocates on one of the two resamples
+# (tools/reloc_cases.py's interception); d = 8, 40, 100 run the kernels padded to 32, 64, 128
+NARROW_RELOC_SEEDS = {
+    8: (0, 8, 11, 24, 28, 29),
+    40: (9, 11, 20, 24, 25, 26),
+    100: (22, 25, 45, 46, 65, 82),
+}
+NARROW_RELOC_GOLDEN = "engine/narrow_reloc.npz"  # under tests/golden/
+
+
+def _narrow_reloc_case(seed, d):
+    """_reloc_case's duplicate-heavy rows at the narrow engine's sizes: n in [120, 260), d given,
+    float32."""
+    rng = np.random.default_rng(seed)
+    n = int(rng.integers(120, 260))
+    nd = int(rng.integers(5, 12))
+    base = rng.normal(size=(nd, d)) * rng.uniform(0.5, 5)
+    X = (base[rng.integers(0, nd, n)] + rng.normal(size=(n, d)) * rng.choice([0, 0.01, 0.3])).astype(np.float32)
+    return X, int(rng.integers(3, nd + 3))
+
+
+def narrow_reloc_run(seed, d):
+    """One pinned case through the d <= 128 engine: what the fixture stores and the test compares."""
+    X, K = _narrow_reloc_case(seed, d)
+    idx, labs, inert, nit, stats = run_gpu(X, [K], H=2, frac=0.8, seed=seed)
+    return X, dict(labels=labs[0].astype(np.uint8), inertia_bits=inert[0].view(np.uint32),
+                   n_iter=nit[0].astype(np.int32), relocations=np.int64(stats[3]))
+
+
+def test_narrow_relocation_is_pinned():
+    """Empty-cluster relocation of the d <= 128 engine at its three padded widths (32, 64, 128).
+    The farthest rows tie on this duplicate-heavy data and numpy's argpartition order among ties
+    is unspecified, so sklearn is not the expectation: the engine's lowest-index rule is pinned
+    against the engine's own output at the commit named in the fixture (labels, inertia bits,
+    n_iter and the relocation counter, all exact; tests/golden/make_narrow_reloc.py)."""
+    import os
+
+    from tests.conftest import GOLDEN, digest
+
+    z = np.load(os.path.join(GOLDEN, NARROW_RELOC_GOLDEN), allow_pickle=False)
+    for d, seeds in NARROW_RELOC_SEEDS.items():
+        relocations = 0
+        for seed in seeds:
+            X, got = narrow_reloc_run(seed, d)
+            key = f"d{d}_s{seed}_"
+            assert digest(X) == str(z[key + "x_sha256"]), (d, seed)
+            print(f"narrow relocation d={d} seed={seed}: relocations {got['relocations']}, "
+                  f"n_iter {got['n_iter'].tolist()}, inertia {got['inertia_bits'].view(np.float32).tolist()}")
+            for name, val in got.items():
+                np.testing.assert_array_equal(val, z[key + name], err_msg=f"d={d} seed={seed} {name}")
+            relocations += int(got["relocations"])
+        assert relocations > 0, f"d={d}: no relocation, the cases no longer exercise it"
+
+
 def test_sparse_mstep_against_dense(monkeypatch):
     """The sparse M-step (d = 128: f64 running sums of exact rows updated from change lists)
     against the dense one (f32 MFMA sums of the 22-bit row image every iteration), on C3-shaped
