@@ -61,6 +61,13 @@ SIGNATURES = {
     "cc_linkage_mst_workspace_bytes": (ctypes.c_size_t, [_c_int]),
     "cc_linkage_mst": (_c_int, [_vp, _c_int, _vp, _vp, ctypes.c_size_t, _vp]),
     "cc_linkage_check": (_c_int, [_vp, ctypes.c_size_t, _vp]),
+    "cc_euclidean": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp]),
+    "cc_hc_gather": (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _vp, _vp]),
+    "cc_hc_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int]),
+    "cc_hc_nnchain_batched": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _c_sz, _vp]),
+    "cc_hc_check": (_c_int, [_vp, _c_int, _vp]),
+    "cc_hc_cut": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _c_i64, _c_i64,
+                           _vp, _c_sz, _vp]),
     "cc_kmeans_f64_workspace_bytes": (_c_sz, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int]),
     "cc_kmeans_f64": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp,
                                _c_int, _c_int, _c_int, _c_dbl, _vp, _c_int, _vp, _vp, _c_int, _vp,

@@ -10,7 +10,10 @@ What runs where (``fit``):
   resampling      numpy-RandomState replay on the device (libccmi cc_resample_device /
                   cc_resample_device_wide) or on host threads (cc_resample_indices)
   clustering      default clusterer (KMeans) -> all (h, K, init) problems in batched
-                  gfx950 launches (cc_kmeans_batched); any other plugin clusterer
+                  gfx950 launches (cc_kmeans_batched); AgglomerativeClustering (ward /
+                  average / complete, euclidean) -> one dendrogram per resample on the
+                  device, cut at every K (cc_euclidean, cc_hc_nnchain_batched,
+                  cc_hc_cut; ``hierarchical``); any other plugin clusterer
                   (e.g. GaussianMixture) keeps the reference's host fit_predict per
                   (K, h) and only its labels go to the GPU (hybrid path)
   I, M, histogram int8-MFMA tiles of the upper triangle (cc_cosample / cc_coassoc)
@@ -65,6 +68,58 @@ def _is_default_kmeans(est) -> bool:
             and p.get("n_init") is not None)
 
 
+HC_LINKAGES = ('ward', 'average', 'complete')
+
+
+def _hc_linkage(est):
+    """The linkage of an AgglomerativeClustering that the device trees reproduce (cc_euclidean,
+    cc_hc_nnchain_batched, cc_hc_cut), else None: exactly that type, linkage ward / average /
+    complete, the euclidean metric, no connectivity and no distance threshold."""
+    try:
+        from sklearn.cluster import AgglomerativeClustering
+    except ImportError:  # pragma: no cover
+        return None
+    if type(est) is not AgglomerativeClustering:
+        return None
+    p = est.get_params()
+    link = p.get("linkage")
+    if not isinstance(link, str) or link not in HC_LINKAGES:
+        return None
+    metric = p.get("metric", "euclidean")
+    if not (metric is None or (isinstance(metric, str) and metric in ("euclidean", "l2"))):
+        return None
+    if p.get("connectivity") is not None or p.get("distance_threshold") is not None:
+        return None
+    return link
+
+
+def _is_device_hierarchical(est) -> bool:
+    """AgglomerativeClustering configured so that the device trees reproduce it."""
+    return _hc_linkage(est) is not None
+
+
+def _hc_validate(X, m, Ks):
+    """sklearn's own refusals for the device trees, raised from host values before any launch:
+    non-finite X (check_array's message; X None = checked elsewhere), fewer than 2 samples per
+    resample, and a K above the resample size (_hc_cut's message)."""
+    if X is not None:
+        X = np.asarray(X)
+        if X.dtype.kind == 'f' and not np.isfinite(X).all():
+            if np.isnan(X).any():
+                raise ValueError("Input X contains NaN.")
+            raise ValueError(f"Input X contains infinity or a value too large for dtype('{X.dtype}').")
+        d = X.shape[1] if X.ndim == 2 else 0
+    else:
+        d = 0
+    if m < 2:
+        raise ValueError(f"Found array with {m} sample(s) (shape=({m}, {d})) while a minimum of 2 is "
+                         "required by AgglomerativeClustering.")
+    for K in Ks:
+        if K > m:
+            raise ValueError("Cannot extract more clusters than samples: "
+                             f"{K} clusters were given for a tree with {m} leaves.")
+
+
 class ConsensusClustering:
     """Monti consensus clustering on MI355X.  Drop-in for CC.py:11."""
 
@@ -89,6 +144,7 @@ class ConsensusClustering:
         workspace_budget=None,
         precision='auto',
         resampling='auto',
+        hierarchical='auto',
     ):
         self.K_range = K_range
         self.n_iterations = n_iterations
@@ -117,6 +173,10 @@ class ConsensusClustering:
         # cc_resample_device_wide above), 'host' (native threads, then uploaded), 'auto' =
         # device; identical draws
         self.resampling = resampling
+        # an AgglomerativeClustering base clusterer (ward / average / complete, euclidean): 'auto'
+        # = one tree per resample on the device when the estimator is one the device reproduces,
+        # 'device' = the same but an error when it is not, 'host' = sklearn's fit_predict per (K, h)
+        self.hierarchical = hierarchical
         self.timings_ = {}
         self._rehearsal = None  # (rank, world): bench tooling only, see fit()
 
@@ -133,7 +193,12 @@ class ConsensusClustering:
             self.clusterer.n_components = self._K
         else:
             raise AttributeError('clusterer has neither n_clusters nor n_components attribute')
-        self.clusterer.set_params(random_state=self.random_state, **self.clusterer_options)
+        # a deterministic estimator (AgglomerativeClustering, ...) has no random_state to set
+        opts = dict(self.clusterer_options)
+        get_params = getattr(self.clusterer, 'get_params', None)
+        if get_params is None or 'random_state' in get_params():
+            opts = dict(random_state=self.random_state, **opts)
+        self.clusterer.set_params(**opts)
 
     def _kmeans_params(self):
         """The KMeans parameters after the reference's set_params (clusterer_options win)."""
@@ -178,6 +243,9 @@ class ConsensusClustering:
         # new label matrix and indices reuse that memory instead of growing the pool by a set
         self.labels_ = self._idx_dev = self._idx_host = None
         self.kmeans_inertia_ = self.kmeans_n_iter_ = self.kmeans_stats_ = None
+        self.hc_stats_ = None
+        if self.hierarchical not in ('auto', 'device', 'host'):
+            raise ValueError("hierarchical must be 'auto', 'device' or 'host'")
         self.partial_ = False
         if self._rehearsal is not None:
             # one-GPU rehearsal of rank r's share of a W-rank fit (bench tooling only): the
@@ -223,7 +291,13 @@ class ConsensusClustering:
         t_rs = time.perf_counter()
 
         km = self._kmeans_params()
-        self.backend_ = 'gpu-kmeans' if km is not None else 'host-clusterer'
+        # the estimator as _kmeans_params left it: clusterer_options applied
+        hc = _hc_linkage(self.clusterer) if (Ks and km is None and self.hierarchical != 'host') else None
+        if self.hierarchical == 'device' and hc is None:
+            raise ValueError("hierarchical='device' needs clusterer=AgglomerativeClustering with linkage "
+                             "'ward', 'average' or 'complete', the euclidean metric, no connectivity and "
+                             "no distance_threshold")
+        self.backend_ = 'gpu-kmeans' if km is not None else ('gpu-hc' if hc is not None else 'host-clusterer')
         precision = self.precision
         if precision == 'auto':
             # the reference's clusterer computes in X's dtype (CC.py:282): float64 input keeps
@@ -252,6 +326,8 @@ class ConsensusClustering:
                        inertia=self.kmeans_inertia_, n_iter=self.kmeans_n_iter_, Xhl=Xhl,
                        scale_exp=sexp)
             self.kmeans_stats_ = bk.stats
+        elif Ks and hc is not None:
+            self.hc_stats_ = self._fit_hierarchical(X, wdtype, hc, idx_d, n, m, h0, h1, Ks, labels, dev)
         elif Ks:
             if isinstance(X, torch.Tensor):
                 X = X.cpu().numpy()
@@ -313,6 +389,26 @@ class ConsensusClustering:
         if self.plot_cdf and rank == 0:
             self._plot_cdf()
         return self
+
+    def _fit_hierarchical(self, X, wdtype, link, idx_d, n, m, h0, h1, Ks, labels, dev):
+        """CC.py:282 for AgglomerativeClustering(linkage=link) on the device: the n x n euclidean
+        distances once (each rank its own), then one tree per resample of [h0, h1), cut at every
+        K, into this rank's columns of the label matrix."""
+        if isinstance(X, torch.Tensor):
+            # a device tensor: the finiteness test runs where X lives (torch, no kernel of ours)
+            _hc_validate(None if bool(torch.isfinite(X).all()) else X.detach().cpu().numpy(), m, Ks)
+            Xd = X.to(dev, torch.float64 if wdtype == np.float64 else torch.float32).contiguous()
+        else:
+            _hc_validate(X, m, Ks)
+            Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=wdtype)).to(dev)
+        budget = self.workspace_budget
+        if budget is not None:
+            engine.hc_plan(n, m, max(h1 - h0, 1), len(Ks), budget)  # too small: raises before any launch
+        Dfull = engine.euclidean(Xd)
+        if not bool(torch.isfinite(Dfull).all()):  # finite X can still overflow the squares
+            raise ValueError("the euclidean distances between the rows of X are not all finite "
+                             "(overflow in float64)")
+        return engine.hc_labels(Dfull, idx_d, h0, h1, Ks, link, labels, budget=budget)
 
     def _check_k_range(self, Ks):
         """Every K of K_range must be an integer in [1, 127] (the uint8 label format and the

@@ -19,6 +19,7 @@
 #include <string>
 
 #include "ccmi_internal.h"
+#include "linkage_shared.hpp"
 
 namespace {
 
@@ -185,69 +186,16 @@ namespace {
 constexpr int LT = 1024;  // threads of the linkage workgroup
 constexpr int NB = 8;     // loads per thread in flight per row pass
 
-__device__ __forceinline__ double lw_update(int method, double dxi, double dyi, int nx, int ny) {
-#pragma clang fp contract(off)  // scipy's products and sum rounded separately (no FMA)
-  if (method == CC_LINK_COMPLETE) return dxi > dyi ? dxi : dyi;  // fmax(d_xi, d_yi)
-  if (method == CC_LINK_WEIGHTED) return 0.5 * (dxi + dyi);
-  // average: (size_x * d_xi + size_y * d_yi) / (size_x + size_y)
-  const double a = static_cast<double>(nx) * dxi;
-  const double b = static_cast<double>(ny) * dyi;
-  return (a + b) / static_cast<double>(nx + ny);
-}
+using cc_link::live;
+using cc_link::lw_update;  // linkage_shared.hpp: shared with the batched trees of hclust.hip
 
-// Block minimum of (v, i): the lower value, ties to the lower index.
 __device__ __forceinline__ void block_argmin(double& v, int& i, double* rv, int* ri) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(v, o);
-    const int oi = __shfl_xor(i, o);
-    if (ov < v || (ov == v && oi < i)) {
-      v = ov;
-      i = oi;
-    }
-  }
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-    rv[w] = v;
-    ri[w] = i;
-  }
-  __syncthreads();
-  v = rv[0];
-  i = ri[0];
-  for (int k = 1; k < LT / 64; ++k)
-    if (rv[k] < v || (rv[k] == v && ri[k] < i)) {
-      v = rv[k];
-      i = ri[k];
-    }
+  cc_link::block_argmin<LT>(v, i, rv, ri);
 }
 
-__device__ __forceinline__ bool live(const unsigned* mask, int i) { return (mask[i >> 5] >> (i & 31)) & 1u; }
-
-// First minimum over live i != x of row[i]: thread tid visits i = base + tid + LT u in increasing
-// order, NB loads in flight per batch.
 __device__ __forceinline__ void row_argmin(const double* row, int n, int x, const unsigned* mask, double& v,
                                            int& bi) {
-  constexpr double INF = __builtin_huge_val();
-  const int tid = threadIdx.x;
-  v = INF;
-  bi = 0x7fffffff;
-  for (int base = 0; base < n; base += LT * NB) {
-    double d[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      const int i = base + tid + LT * u;
-      d[u] = i < n ? row[i] : INF;
-    }
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      const int i = base + tid + LT * u;
-      const bool ok = i < n && i != x && live(mask, i);
-      if (ok && d[u] < v) {
-        v = d[u];
-        bi = i;
-      }
-    }
-  }
+  cc_link::row_argmin<LT, NB>(row, n, x, mask, v, bi);
 }
 
 __global__ __launch_bounds__(LT) void nnchain_kernel(double* __restrict__ D, int n, int method,
@@ -335,7 +283,8 @@ __global__ __launch_bounds__(LT) void nnchain_kernel(double* __restrict__ D, int
       for (int u = 0; u < NB; ++u) {
         const int i = base + tid + LT * u;
         if (i < n && i != y && live(mask, i)) {
-          const double nd = lw_update(method, dx[u], dy[u], nx, ny);
+          const int ni = method == CC_LINK_WARD ? size[i] : 0;
+          const double nd = lw_update(method, dx[u], dy[u], cur, nx, ny, ni);
           ry[i] = nd;
           D[i * nn + y] = nd;
         }
@@ -650,7 +599,8 @@ __global__ __launch_bounds__(LG) void nnchain_grid_kernel(double* __restrict__ D
       for (int u = 0; u < NBG; ++u) {
         const int i = base + tid + LG * u;
         if (i < j1 && i != y && live(mask, i)) {
-          const double nd = lw_update(method, dx[u], dy[u], nx, ny);
+          const int ni = method == CC_LINK_WARD ? size[i] : 0;
+          const double nd = lw_update(method, dx[u], dy[u], cur, nx, ny, ni);
           ry[i] = nd;
           D[i * nn + y] = nd;
         }
@@ -783,7 +733,8 @@ extern "C" int cc_linkage_nnchain(double* D, int n, int method, double* Z, void*
                                   void* stream) {
   const int G = n > 0 ? link_groups(n, nnchain_grid_kernel) : 0;
   if (!D || !Z || n < 2 || !workspace || ws_bytes < nnchain_ws(n, G) ||
-      (method != CC_LINK_AVERAGE && method != CC_LINK_COMPLETE && method != CC_LINK_WEIGHTED) ||
+      (method != CC_LINK_AVERAGE && method != CC_LINK_COMPLETE && method != CC_LINK_WEIGHTED &&
+       method != CC_LINK_WARD) ||
       mask_bytes(n) > MASK_LDS_MAX) {
     cc::set_error("cc_linkage_nnchain: bad arguments");
     return CC_ERR_ARG;

@@ -316,6 +316,7 @@ def consensus(M: torch.Tensor, I: torch.Tensor) -> torch.Tensor:
 
 
 LINKAGE_METHODS = {"average": 0, "complete": 1, "weighted": 2}  # CC_LINK_* (include/ccmi.h)
+_CC_LINK = dict(LINKAGE_METHODS, ward=3)  # ward: euclidean distances only (the base clusterer)
 
 
 def linkage_raw(D: torch.Tensor, method: str) -> torch.Tensor:
@@ -325,7 +326,7 @@ def linkage_raw(D: torch.Tensor, method: str) -> torch.Tensor:
     Z = torch.empty((n - 1, 4), dtype=torch.float64, device=D.device)
     lib = _lib.load()
     ws = torch.empty(int(lib.cc_linkage_workspace_bytes(n)), dtype=torch.uint8, device=D.device)
-    _lib.call("cc_linkage_nnchain", D.data_ptr(), n, LINKAGE_METHODS[method], Z.data_ptr(), ws.data_ptr(),
+    _lib.call("cc_linkage_nnchain", D.data_ptr(), n, _CC_LINK[method], Z.data_ptr(), ws.data_ptr(),
               ws.numel(), stream_ptr())
     _lib.call("cc_linkage_check", ws.data_ptr(), ws.numel(), stream_ptr())
     return Z
@@ -365,3 +366,154 @@ def manhattan(C: torch.Tensor) -> torch.Tensor:
     D = torch.empty((n, n), dtype=torch.float64, device=C.device)
     _lib.call("cc_manhattan", C.data_ptr(), n, d, D.data_ptr(), stream_ptr())
     return D
+
+
+# ---------------------------------------------------------------- hierarchical base clusterer
+
+LINKAGE_METHODS_HC = {"average": 0, "complete": 1, "ward": 3}  # CC_LINK_* of the base clusterer
+
+# With fewer trees than this per launch of cc_hc_nnchain_batched (one workgroup each) the
+# resamples go one after the other through cc_linkage_nnchain, whose grid form spreads one tree
+# over up to 128 workgroups.  Measured on the MI355X at m = 8000 (DESIGN.md K10,
+# profiles/hc/hc_measure.txt): the grid form takes 171 ms a tree; a batched launch takes 168 /
+# 172 / 178 / 203 ms for 1 / 4 / 16 / 64 trees.  Two trees in a launch already take half the time
+# of two grid-form runs; one tree ties (168 against 171 ms) and goes to the grid form, because a
+# budget that holds a single tree means a large m, where the grid form wins (n = 50 000: 1.34
+# against 4.2 s).
+HC_BATCH_CROSSOVER = 2
+
+
+def euclidean(X: torch.Tensor) -> torch.Tensor:
+    """float64 [n, n] on the device: squareform(pdist(X, 'euclidean')) bit for bit, for the
+    float32 or float64 rows X [n, d] (cc_euclidean)."""
+    assert X.dim() == 2 and X.is_cuda and X.is_contiguous() and X.dtype in (torch.float32, torch.float64)
+    n, d = X.shape
+    D = torch.empty((n, n), dtype=torch.float64, device=X.device)
+    with timed("cc_euclidean"):
+        _lib.call("cc_euclidean", X.data_ptr(), int(X.dtype == torch.float64), n, d, D.data_ptr(),
+                  stream_ptr(X.device))
+    return D
+
+
+def hc_gather(Dfull: torch.Tensor, idx_bm: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """float64 [B, m, m]: out[b] = Dfull[idx[b]][:, idx[b]] (cc_hc_gather)."""
+    assert Dfull.dtype == torch.float64 and Dfull.dim() == 2 and Dfull.is_contiguous()
+    assert idx_bm.dtype == torch.int32 and idx_bm.dim() == 2 and idx_bm.is_contiguous()
+    B, m = idx_bm.shape
+    if out is None:
+        out = torch.empty((B, m, m), dtype=torch.float64, device=Dfull.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == B * m * m
+    with timed("cc_hc_gather"):
+        _lib.call("cc_hc_gather", Dfull.data_ptr(), Dfull.shape[0], idx_bm.data_ptr(), B, m,
+                  out.data_ptr(), stream_ptr(Dfull.device))
+    return out.view(B, m, m)
+
+
+def hc_workspace(m: int, B: int, nK: int, device) -> torch.Tensor:
+    return torch.empty(int(_lib.load().cc_hc_workspace_bytes(int(m), int(B), int(nK))), dtype=torch.uint8,
+                       device=device)
+
+
+def hc_nnchain_batched(Db: torch.Tensor, method: str, ws: torch.Tensor = None) -> torch.Tensor:
+    """nn_chain's raw merges [B, m-1, 4] (x, y, distance, size in merge order) of the B trees over
+    the symmetric float64 [B, m, m] distances Db (overwritten): cc_hc_nnchain_batched, then
+    cc_hc_check, which raises when a tree's status word is set."""
+    assert Db.dtype == torch.float64 and Db.dim() == 3 and Db.shape[1] == Db.shape[2] and Db.is_contiguous()
+    B, m, _ = Db.shape
+    if ws is None:
+        ws = hc_workspace(m, B, 0, Db.device)
+    Z = torch.empty((B, m - 1, 4), dtype=torch.float64, device=Db.device)
+    with timed("cc_hc_nnchain_batched"):
+        _lib.call("cc_hc_nnchain_batched", Db.data_ptr(), B, m, LINKAGE_METHODS_HC[method], Z.data_ptr(),
+                  ws.data_ptr(), ws.numel(), stream_ptr(Db.device))
+    _lib.call("cc_hc_check", ws.data_ptr(), B, stream_ptr(Db.device))
+    return Z
+
+
+def hc_cut(Z: torch.Tensor, idx_bm: torch.Tensor, Ks_d: torch.Tensor, h_begin: int, labels: torch.Tensor,
+           ws: torch.Tensor = None):
+    """labels[k, idx[b, r], h_begin + b] = the cluster of leaf r in the Ks[k]-cluster cut of tree b
+    (cc_hc_cut), from the raw merges Z [B, m-1, 4]; the merges' stable ranks by distance come
+    from torch.sort on the batch.  labels: uint8 [nK, n, Hpad] contiguous."""
+    B, m1, _ = Z.shape
+    m = m1 + 1
+    assert Z.dtype == torch.float64 and Z.is_contiguous()
+    assert idx_bm.dtype == torch.int32 and tuple(idx_bm.shape) == (B, m) and idx_bm.is_contiguous()
+    assert Ks_d.dtype == torch.int32 and Ks_d.is_cuda and Ks_d.is_contiguous()
+    nK = Ks_d.numel()
+    assert labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous() and labels.shape[0] == nK
+    if ws is None:
+        ws = hc_workspace(m, B, nK, Z.device)
+    with timed("cc_hc_cut"):
+        order = torch.sort(Z[:, :, 2], dim=1, stable=True).indices
+        rank = torch.empty((B, m1), dtype=torch.int32, device=Z.device)
+        rank.scatter_(1, order, torch.arange(m1, dtype=torch.int32, device=Z.device).expand(B, m1))
+        _lib.call("cc_hc_cut", Z.data_ptr(), rank.data_ptr(), idx_bm.data_ptr(), B, m, Ks_d.data_ptr(), nK,
+                  int(h_begin), labels.data_ptr(), labels.shape[1], labels.shape[2], ws.data_ptr(), ws.numel(),
+                  stream_ptr(Z.device))
+
+
+def hc_tree_bytes(m: int, nK: int) -> int:
+    """Device bytes one tree of a batch needs: its m x m float64 distances, its merges and their
+    sort (values, indices, ranks), the chain state and the cut's links (cc_hc_workspace_bytes)."""
+    m, nK = int(m), int(nK)
+    return 8 * m * m + (32 + 8 + 8 + 4) * (m - 1) + 8 * m + 4 * nK * m + 512  # 512: status word, alignment
+
+
+def hc_plan(n: int, m: int, nh: int, nK: int, budget: int):
+    """(B, route) for the nh resamples of a rank: B = min(nh, (budget - 8 n^2) // bytes per tree)
+    trees per launch; route 'batched' (cc_hc_nnchain_batched on B trees) or 'sequential' (one
+    tree at a time through cc_linkage_nnchain, grid form for large m) when the budget holds fewer
+    trees than HC_BATCH_CROSSOVER and fewer than the rank has.  Raises when the n x n distances
+    and one tree do not fit the budget."""
+    per = hc_tree_bytes(m, nK)
+    fit = (int(budget) - 8 * int(n) * int(n)) // per
+    if fit < 1:
+        raise ValueError(
+            f"workspace_budget = {int(budget)} bytes cannot hold the hierarchical clusterer: the n x n "
+            f"float64 distances ({8 * int(n) * int(n)} bytes) and one tree of m = {int(m)} "
+            f"({per} bytes) are needed")
+    B = max(1, min(int(nh), int(fit)))
+    route = 'sequential' if B < min(int(nh), HC_BATCH_CROSSOVER) else 'batched'
+    return B, route
+
+
+def hc_labels(Dfull: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, method: str,
+              labels: torch.Tensor, budget: int = None, route: str = 'auto') -> dict:
+    """Fill labels[k, idx[h, r], h] for h in [h0, h1) and every K of Ks with the K-cluster cut of
+    the `method` tree over Dfull[idx[h]][:, idx[h]] (AgglomerativeClustering.fit_predict of every
+    (h, K), one tree per h).  idx_d: int32 [H, m] on the device.  budget: device bytes for Dfull
+    and the trees (default: half the free memory plus Dfull, which exists already).  Returns the
+    plan that ran: dict(route, batch, launches)."""
+    n = Dfull.shape[0]
+    m = idx_d.shape[1]
+    nh = h1 - h0
+    dev = Dfull.device
+    nK = len(Ks)
+    if budget is None:
+        budget = 8 * n * n + torch.cuda.mem_get_info(dev)[0] // 2
+    B, planned = hc_plan(n, m, max(nh, 1), nK, budget)
+    if route == 'auto':
+        route = planned
+    if route not in ('batched', 'sequential'):
+        raise ValueError("route must be 'auto', 'batched' or 'sequential'")
+    if route == 'sequential':
+        B = 1
+    stats = dict(route=route, batch=B, launches=0)
+    if nh <= 0 or nK == 0:
+        return stats
+    Ks_d = torch.tensor([int(K) for K in Ks], dtype=torch.int32, device=dev)
+    ws = hc_workspace(m, B, nK, dev)
+    Db = torch.empty((B, m, m), dtype=torch.float64, device=dev)
+    for a in range(h0, h1, B):
+        b = min(a + B, h1)
+        rows = idx_d[a:b].contiguous()
+        D = hc_gather(Dfull, rows, out=Db[:b - a])
+        if route == 'batched':
+            Z = hc_nnchain_batched(D, method, ws)
+        else:
+            with timed("cc_linkage_nnchain"):
+                Z = linkage_raw(D[0], method).unsqueeze(0)
+        hc_cut(Z, rows, Ks_d, a, labels, ws)
+        stats['launches'] += 1
+    return stats

@@ -27,6 +27,9 @@
  *                         (sklearn KMeans: k-means++ init, Lloyd, best of n_init)
  *   cc_kmeans_f64         the same at float64 for float64 input
  *   cc_kmeans_fit         CC.py:282 in one call (plans and launches one of the three above)
+ *   cc_euclidean, cc_hc_gather, cc_hc_nnchain_batched, cc_hc_cut
+ *                         CC.py:282 for AgglomerativeClustering (ward / average / complete,
+ *                         euclidean): one tree per resample, cut at every K
  */
 #ifndef CCMI_H
 #define CCMI_H
@@ -186,6 +189,9 @@ int cc_manhattan(const float* C, int n, int d, double* D, void* stream);
 #define CC_LINK_AVERAGE 0
 #define CC_LINK_COMPLETE 1
 #define CC_LINK_WEIGHTED 2
+/* Ward on euclidean (not squared) distances, scipy's _ward update:
+ * t = 1 / (nx + ny + ni); sqrt((ni+nx) t dxi^2 + (ni+ny) t dyi^2 - ni t dxy^2). */
+#define CC_LINK_WARD 3
 size_t cc_linkage_workspace_bytes(int n);
 int cc_linkage_nnchain(double* D, int n, int method, double* Z, void* workspace, size_t ws_bytes,
                        void* stream);
@@ -205,6 +211,45 @@ int cc_linkage_mst(const double* D, int n, double* out, void* workspace, size_t 
  * stream and returns CC_ERR_HIP if a grid barrier of the linkage timed out (its output is then
  * invalid), else CC_OK. */
 int cc_linkage_check(const void* workspace, size_t ws_bytes, void* stream);
+
+/* Hierarchical base clusterer (CC.py:282 with AgglomerativeClustering(linkage = ward | average |
+ * complete, metric = euclidean), which is scipy.cluster.hierarchy.linkage(X[idx[h]], method,
+ * 'euclidean') cut by _hc_cut): one tree per resample serves every K.
+ *
+ * cc_euclidean: D [n][n] float64 = squareform(pdist(X, 'euclidean')) bit for bit: sqrt of the
+ * float64 sum over k, in increasing k, of (u_k - v_k)^2 with no FMA; symmetric, zero diagonal.
+ * X [n][d] float32 (is_f64 = 0; converted exactly) or float64 (is_f64 = 1). */
+int cc_euclidean(const void* X, int is_f64, int n, int d, double* D, void* stream);
+
+/* Db [B][m][m]: Db[b][a][c] = Dfull[idx[b][a]][idx[b][c]] for B resamples (idx [B][m] int32,
+ * values in [0, n)). */
+int cc_hc_gather(const double* Dfull, int n, const int* idx, int B, int m, double* Db, void* stream);
+
+/* Workspace of cc_hc_nnchain_batched (nK = 0) or of cc_hc_cut for B trees of m leaves and nK
+ * values of K; a workspace sized for nK serves both calls. */
+size_t cc_hc_workspace_bytes(int m, int B, int nK);
+
+/* scipy's nn_chain on B trees at once, one workgroup per tree (no communication between
+ * workgroups): D [B][m][m] float64 symmetric, overwritten; Z [B][m-1][4] float64 receives each
+ * tree's (x, y, distance, size) per merge in merge order (x < y: slot x dies, slot y keeps the
+ * union), as cc_linkage_nnchain writes them.  method: CC_LINK_*.  The workspace begins with one
+ * status word per tree: a tree whose scan finds no neighbour (non-finite distances) stops there
+ * and sets its word; cc_hc_check reports it. */
+int cc_hc_nnchain_batched(double* D, int B, int m, int method, double* Z, void* workspace, size_t ws_bytes,
+                          void* stream);
+
+/* After cc_hc_nnchain_batched on `stream`: synchronises the stream and returns CC_ERR_HIP when a
+ * tree's status word is set (its Z is invalid), else CC_OK. */
+int cc_hc_check(const void* workspace, int B, void* stream);
+
+/* The K-cluster cuts of B trees: for tree b (resample h_begin + b), K index k and leaf r,
+ * labels[k][idx[b][r]][h_begin + b] = cluster id in [0, Ks[k]), every id used (numbering: the
+ * clusters' surviving slots in increasing order).  Z [B][m-1][4] raw merges; rank [B][m-1] int32:
+ * the position of each merge in the stable sort of its tree's merges by distance; idx [B][m]
+ * int32; Ks [nK] int32 on the device, 1 <= Ks[k] <= m; labels uint8 [nK][n][ldl]. */
+int cc_hc_cut(const double* Z, const int* rank, const int* idx, int B, int m, const int* Ks, int nK,
+              int h_begin, uint8_t* labels, int64_t n, int64_t ldl, void* workspace, size_t ws_bytes,
+              void* stream);
 
 /* Batched k-means for every (resample h, K, init) problem, replacing the per-(K, h)
  * clusterer.fit_predict(X[indices]) of CC.py:282 for the default clusterer
