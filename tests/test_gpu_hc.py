@@ -1,7 +1,10 @@
 """Hierarchical base clusterer on the device (cc_euclidean, cc_hc_gather, cc_hc_nnchain_batched,
 cc_hc_cut): every stage against scipy / sklearn on the host, exactly, and the whole fit against
 the oracle with AgglomerativeClustering as its clusterer.  Every batched run goes through
-cc_hc_check, so a tree with a set status word fails the test that ran it."""
+cc_hc_check, so a tree with a set status word fails the test that ran it
+(test_check_reads_every_status_word shows that it does).  The trees and cuts that only large m
+reach (state or links in the workspace, a second row pass) and the deep synthetic trees of
+tests/hc_ref.py are here too."""
 import functools
 
 import numpy as np
@@ -11,8 +14,9 @@ from scipy.cluster.hierarchy import linkage
 from scipy.spatial.distance import pdist, squareform
 from sklearn.cluster import AgglomerativeClustering
 
-from consensus_clustering_amd import ConsensusClustering, engine, post
+from consensus_clustering_amd import ConsensusClustering, _lib, engine, post
 from oracle import cc_oracle as O
+from tests import hc_ref
 from tests.conftest import load_fixture
 
 pytestmark = pytest.mark.gpu
@@ -44,14 +48,34 @@ def test_euclidean_k_slab_edge():
         np.testing.assert_array_equal(engine.euclidean(_dev(X)).cpu().numpy(), squareform(pdist(X, "euclidean")))
 
 
-def test_gather_equals_fancy_indexing():
+@pytest.mark.parametrize("n,d,dtype", [(1, 1, np.float32), (2, 3, np.float64), (64, 16, np.float64),
+                                       (63, 17, np.float64), (129, 33, np.float64)])
+def test_euclidean_at_the_edges(n, d, dtype):
+    """A single row (one tile, one stored entry), two rows, exactly one tile of exactly one k slab,
+    one row and one k short of / past them, and a third tile row with a third k slab of one."""
+    X = np.random.RandomState(n + d).randn(n, d).astype(dtype)
+    got = engine.euclidean(_dev(X)).cpu().numpy()
+    np.testing.assert_array_equal(got, squareform(pdist(X, "euclidean")))
+    np.testing.assert_array_equal(got, got.T)
+    np.testing.assert_array_equal(np.diag(got), 0.0)
+
+
+def _gather_case(n, m, B):
     rs = np.random.RandomState(0)
-    n, m, B = 50, 33, 3
     D = rs.rand(n, n)
     idx = np.stack([rs.permutation(n)[:m] for _ in range(B)]).astype(np.int32)
     got = engine.hc_gather(_dev(D), _dev(idx)).cpu().numpy()
     for b in range(B):
         np.testing.assert_array_equal(got[b], D[idx[b]][:, idx[b]])
+
+
+def test_gather_equals_fancy_indexing():
+    _gather_case(50, 33, 3)
+
+
+def test_gather_second_column_block():
+    """m = 300: a second 256-wide column block with a ragged edge."""
+    _gather_case(400, 300, 2)
 
 
 # ---------------------------------------------------------------- batched nn_chain
@@ -89,7 +113,122 @@ def test_batched_nn_chain_with_ties(link):
         np.testing.assert_array_equal(Z, linkage(X[idx[b]], link, "euclidean"), err_msg=f"tree {b}")
 
 
+@pytest.mark.parametrize("m,link", [(6050, "complete"), (8195, "ward"), (8195, "average"), (8195, "complete")])
+def test_batched_nn_chain_large_trees_equal_scipy(m, link):
+    """The two branches of nnchain_batched_kernel that only a large tree takes (hclust.hip).
+
+    Chain state in the workspace: state_in_lds(m) asks 4 ceil(m / 32) bytes of live mask plus 8 m
+    bytes of sizes and chain to fit HC_LDS_STATE_MAX = 49152.  m = 6049 has 190 mask words,
+    760 + 48392 = 49152, the last m in LDS; m = 6050 takes 49160 bytes, the first whose
+    size[] / chain[] sit in global memory at state + b * 2 * m.
+
+    A second row pass: row_argmin<T, NBH> and the Lance-Williams loop step by T * NBH =
+    HC_T_LARGE * NBH = 1024 * 8 = 8192 slots, so m <= 8192 is one pass and m = 8193 the first
+    with two; m = 8195 puts three leaves (not one lane's worth) into the second pass.  Ward is the
+    method whose update reads size[i] there.
+
+    Two trees: the second one's state is at a non-zero offset.  Against scipy, exactly."""
+    rs = np.random.RandomState(m)
+    n, B = m + 7, 2
+    X = rs.randn(n, 5).astype(np.float32)
+    idx = np.stack([rs.permutation(n)[:m] for _ in range(B)]).astype(np.int32)
+    trees = _trees(X, idx, link)
+    torch.cuda.empty_cache()  # about 1.6 GB of distances at m = 8195
+    for b, Z in enumerate(trees):
+        np.testing.assert_array_equal(Z, linkage(X[idx[b]], link, "euclidean"), err_msg=f"tree {b}")
+
+
+def test_check_reads_every_status_word():
+    """cc_hc_check over more trees than one of its 1024-word chunks: 1030 trees of three leaves.
+    All finite: the trees on both sides of the chunk edge equal scipy.  A tree whose distances
+    are all +inf finds no neighbour (the kernel's defined error return: the scan's sentinel is
+    refused before anything is indexed), and the call raises naming the first such tree, also
+    when that tree's status word lies in the second chunk."""
+    rs = np.random.RandomState(7)
+    B, m = 1030, 3
+    P = rs.rand(B, m, 2)
+    Db = np.stack([squareform(pdist(P[b], "euclidean")) for b in range(B)])
+    Z = engine.hc_nnchain_batched(_dev(Db), "average").cpu().numpy()
+    for b in (0, 1023, 1024, 1029):
+        np.testing.assert_array_equal(post.linkage_finish(Z[b], m), linkage(P[b], "average", "euclidean"),
+                                      err_msg=f"tree {b}")
+    off = ~np.eye(m, dtype=bool)
+    for trees, first in (((1027,), 1027), ((5, 1027), 5)):
+        bad = Db.copy()
+        for b in trees:
+            bad[b][off] = np.inf
+        with pytest.raises(_lib.CCMIError, match=f"tree {first} found no neighbour"):
+            engine.hc_nnchain_batched(_dev(bad), "average")
+
+
 # ---------------------------------------------------------------- cut
+
+def _cut_synthetic(m, Zs, Ks, seed):
+    """cc_hc_cut alone on the raw merges Zs (one tree each) against hc_ref.reference_cut: leaf r
+    of tree b is item idx[b, r] of n > m, the trees fill columns [3, 3 + B) of 128, and the
+    whole label matrix is compared, so every cell the call does not own must still be 0xFF."""
+    rs = np.random.RandomState(seed)
+    B, n, h_begin = len(Zs), m + 9, 3
+    idx = np.stack([rs.permutation(n)[:m] for _ in range(B)]).astype(np.int32)
+    L = engine.new_label_matrix(len(Ks), n, engine.pad_h(8), "cuda")
+    engine.hc_cut(_dev(np.stack(Zs)), _dev(idx), torch.tensor(Ks, dtype=torch.int32, device="cuda"), h_begin, L)
+    want = np.full((len(Ks), n, engine.pad_h(8)), 0xFF, dtype=np.uint8)
+    for b, Z in enumerate(Zs):
+        for k, K in enumerate(Ks):
+            ref = hc_ref.reference_cut(Z, m, K)
+            assert sorted(set(ref.tolist())) == list(range(K))
+            if K == m:  # every leaf alone: its id is its slot's rank
+                np.testing.assert_array_equal(ref, np.arange(m))
+            want[k, idx[b], h_begin + b] = ref
+    np.testing.assert_array_equal(L.cpu().numpy(), want)
+
+
+def _synthetic_pair(m, kind, ties=False):
+    """Two trees of one kind with different merges: a caterpillar with increasing distances
+    (the cut keeps the bottom of the chain) and with decreasing ones (it keeps the top); two
+    draws of random merges, with distances in [0, 4) for ties."""
+    rs = np.random.RandomState(m)
+    Zs = [hc_ref.synthetic_merges(m, kind, rs) for _ in range(2)]
+    if kind != "random":
+        Zs[1][:, 2] = Zs[1][::-1, 2].copy()
+    if ties:
+        for Z in Zs:
+            Z[:, 2] = rs.randint(0, 4, size=m - 1)
+    return Zs
+
+
+@pytest.mark.parametrize("kind", ["chain", "bypass", "random"])
+@pytest.mark.parametrize("m", [2, 3, 63, 64, 65, 1023, 1024, 1025])
+def test_cut_of_synthetic_trees(kind, m):
+    """ceil(log2 m) rounds of pointer jumping on both sides of a power of two; the caterpillars
+    (slot j dies into j + 1) are m - 1 and m - 2 links deep, which no tree of blob data is.  A
+    round too few shows in 'bypass' at K = 2 (tests/hc_ref.py says why not in 'chain') where
+    ceil(log2 (m - 2)) = ceil(log2 m): m = 63, 64, 1023, 1024; at 2^p + 1 the kernel has a round
+    to spare."""
+    Ks = sorted({K for K in (1, 2, 3, 5, min(m, 127)) if K <= m})
+    _cut_synthetic(m, _synthetic_pair(m, kind), Ks, m)
+
+
+@pytest.mark.parametrize("kind", ["chain", "bypass", "random"])
+def test_cut_at_k_equal_to_m(kind):
+    """K = m = 127 keeps no merge: every leaf's id is its slot; K = m - 1 keeps one."""
+    _cut_synthetic(127, _synthetic_pair(127, kind), [1, 126, 127], 127)
+
+
+def test_cut_ranks_tied_distances_stably():
+    _cut_synthetic(300, _synthetic_pair(300, "random", ties=True), [1, 2, 3, 5, 127], 300)
+
+
+@pytest.mark.parametrize("kind", ["chain", "bypass", "random"])
+@pytest.mark.parametrize("m", [11915, 11916])
+def test_cut_with_links_in_lds_and_in_the_workspace(kind, m):
+    """link_in_lds(m) asks 4 ceil(m / 32) bytes of root mask plus 4 m bytes of links to fit
+    HC_LDS_LINK_MAX = 49152: m = 11915 has 373 mask words, 1492 + 47660 = 49152, the last m with
+    the links in LDS; m = 11916 is the first that jumps pointers in global memory, at
+    links + (b * nK + k) * m.  The caterpillars there are the deep trees on that path, and need
+    every one of its ceil(log2 m) = 14 rounds (2^13 < m - 2)."""
+    _cut_synthetic(m, _synthetic_pair(m, kind), [1, 2, 7, 127], m)
+
 
 CUT_KS = list(range(1, 10)) + [127]
 
@@ -140,6 +279,19 @@ def test_range_split_and_routes_agree():
     whole = _labels_for("ward", [(0, 5)])
     np.testing.assert_array_equal(_labels_for("ward", [(0, 2), (2, 5)]), whole)
     np.testing.assert_array_equal(_labels_for("ward", [(0, 5)], route="sequential"), whole)
+
+
+def test_planner_split_with_a_short_last_batch():
+    """A budget for two trees and five resamples: hc_labels itself launches 2, 2 and 1 trees on
+    a workspace sized for two, and fills the labels of the one-launch run."""
+    X, idx = _cut_case()
+    n = X.shape[0]
+    per = engine.hc_tree_bytes(idx.shape[1], len(CUT_KS))
+    L = engine.new_label_matrix(len(CUT_KS), n, engine.pad_h(len(idx)), "cuda")
+    stats = engine.hc_labels(engine.euclidean(_dev(X)), _dev(idx), 0, 5, CUT_KS, "ward", L,
+                             budget=8 * n * n + 2 * per + per // 2)
+    assert stats == dict(route="batched", batch=2, launches=3)
+    np.testing.assert_array_equal(L.cpu().numpy(), _labels_for("ward", [(0, 5)]))
 
 
 # ---------------------------------------------------------------- end to end

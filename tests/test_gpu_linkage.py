@@ -1,6 +1,7 @@
 """Device linkage of predict() (cc_linkage_nnchain): its raw merges equal the oracle's
 restatement of scipy's nn_chain bit for bit (ties included), and predict() runs at the headline
 n = 50 000 (CC.py:292-314), recovering a planted block structure."""
+import functools
 import time
 
 import numpy as np
@@ -14,13 +15,13 @@ from oracle import cc_oracle as O
 pytestmark = pytest.mark.gpu
 
 
-def _distances(n, seed, ties=False):
+def _distances(n, seed, ties=False, metric="cityblock"):
     rs = np.random.RandomState(seed)
     X = rs.rand(n, 6).astype(np.float32)
     if ties:
         X = np.round(X * 3) / 3
         X[n // 2:] = X[: n - n // 2]
-    return squareform(pdist(X, "cityblock"))
+    return squareform(pdist(X, metric))
 
 
 @pytest.mark.parametrize("method", ["average", "complete", "weighted"])
@@ -110,6 +111,28 @@ def test_grid_linkage_equals_oracle(G, n, seed, ties, monkeypatch):
     _lib.call("cc_linkage_mst", Dd.data_ptr(), n, out.data_ptr(), ws.data_ptr(), ws.numel(), engine.stream_ptr())
     _lib.call("cc_linkage_check", ws.data_ptr(), ws.numel(), engine.stream_ptr())
     np.testing.assert_array_equal(out.cpu().numpy(), O.mst_prim(D))
+
+
+@functools.lru_cache(maxsize=None)
+def _method_case(n, seed, method):
+    """Tied distances (euclidean for ward, whose update is meant for them) and the oracle's merges."""
+    D = _distances(n, seed, True, "euclidean" if method == "ward" else "cityblock")
+    D.setflags(write=False)
+    return D, O.nn_chain(D, method)
+
+
+@pytest.mark.parametrize("G", [0, 2, 16])
+@pytest.mark.parametrize("n,seed", [(257, 1), (2000, 3)])
+@pytest.mark.parametrize("method", ["complete", "weighted", "ward"])
+def test_grid_linkage_every_method_equals_oracle(method, n, seed, G, monkeypatch):
+    """The methods that test_grid_linkage_equals_oracle leaves out, in the one-workgroup kernel
+    and on 2 and 16 workgroups.  Ward is the one update that reads size[i], of which every
+    workgroup of the grid form keeps a private copy; it is the route of a one-tree budget of the
+    hierarchical base clusterer."""
+    monkeypatch.setenv("CCMI_LINK_G", str(G))
+    D, want = _method_case(n, seed, method)
+    got = engine.linkage_raw(torch.from_numpy(D.copy()).cuda(), method).cpu().numpy()
+    np.testing.assert_array_equal(got, want)
 
 
 def test_grid_linkage_while_another_stream_is_busy(monkeypatch):

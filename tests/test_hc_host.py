@@ -1,6 +1,7 @@
 """Host side of the hierarchical base clusterer (no GPU): which estimators are routed to the
 device trees, ``_set_clusterer_K`` on an estimator without ``random_state``, sklearn's refusals
-raised from host values, and the batch planner."""
+raised from host values, the batch planner, and the reference cut of tests/hc_ref.py that the
+device cut is held to."""
 import numpy as np
 import pytest
 from sklearn.cluster import AgglomerativeClustering, KMeans
@@ -129,3 +130,31 @@ def test_batch_planner():
         engine.hc_plan(n, m, nh, nK, full + per - 1)
     with pytest.raises(ValueError, match="workspace_budget"):
         engine.hc_plan(n, m, nh, nK, 1 << 20)
+
+
+def _same_partition(a, b):
+    pairs = set(zip(np.asarray(a).tolist(), np.asarray(b).tolist()))
+    return len(pairs) == len({p for p, _ in pairs}) == len({q for _, q in pairs})
+
+
+@pytest.mark.parametrize("kind", ["chain", "bypass", "random"])
+@pytest.mark.parametrize("m", [2, 3, 64, 65, 300])
+def test_reference_cut_is_the_cut_of_the_finished_tree(kind, m):
+    """tests/hc_ref.py, which the device cut is compared with: reference_cut's partition of a
+    synthetic tree (the caterpillars with increasing distances; random merges with tied ones) is
+    sklearn's _hc_cut of the tree that linkage() finishes from the same merges, and its ids are
+    exactly [0, K)."""
+    from consensus_clustering_amd import post
+    from tests import hc_ref
+
+    rs = np.random.RandomState(m)
+    Z = hc_ref.synthetic_merges(m, kind, rs)
+    assert Z.shape == (m - 1, 4) and (Z[:, 0] < Z[:, 1]).all() and Z[-1, 3] == m
+    assert len(set(Z[:, 0].tolist())) == m - 1  # every slot dies at most once
+    if kind == "random":
+        Z[:, 2] = rs.randint(0, 4, size=m - 1)
+    children = post.linkage_finish(Z, m)[:, :2].astype(np.int64)
+    for K in sorted({K for K in (1, 2, 3, min(m, 127)) if K <= m}):
+        got = hc_ref.reference_cut(Z, m, K)
+        assert sorted(set(got.tolist())) == list(range(K)), (m, K)
+        assert _same_partition(got, post.hc_cut(K, children, m)), (m, K)

@@ -29,6 +29,21 @@ def test_oracle_nn_chain_matches_scipy(method, seed, ties):
     np.testing.assert_array_equal(Z, linkage(squareform(D, checks=False), method=method))
 
 
+@pytest.mark.parametrize("method", ["ward", "average", "complete"])
+@pytest.mark.parametrize("n,seed,ties", [(3, 0, True), (257, 1, True), (600, 2, False)])
+def test_oracle_nn_chain_matches_scipy_on_euclidean(method, n, seed, ties):
+    """The base clusterer's call, linkage(X, method, 'euclidean'), Ward's update included (the
+    oracle's float64 restatement of scipy's _ward), bit for bit, with and without ties."""
+    rs = np.random.RandomState(seed)
+    X = rs.rand(n, 6).astype(np.float32)
+    if ties:
+        X = np.round(X * 3) / 3
+        X[n // 2:] = X[: n - n // 2]
+    D = squareform(pdist(X, "euclidean"))
+    Z = post.linkage_finish(O.nn_chain(D, method), n)
+    np.testing.assert_array_equal(Z, linkage(X, method, "euclidean"))
+
+
 @pytest.mark.parametrize("method", ["average", "complete"])
 @pytest.mark.parametrize("K", [2, 3, 7])
 def test_hc_cut_matches_agglomerative(method, K):
