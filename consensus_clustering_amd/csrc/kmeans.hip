@@ -140,7 +140,10 @@ __host__ __device__ constexpr int dist_cost() { return KM_COST_DIST_NARROW; }
 // workgroup 0, added into stats[8 + 8 * wave + k] (k: issue, dist, estep, mstep, commit,
 // barrier) and stats[72..75] (sweep prologue, post-processing, unit setup, output); from all
 // workgroups, sweep cycles and counts by width (stats[80..], [96..]) and of the sweeps that
-// carry seeding items (stats[110], [111]).
+// carry seeding items (stats[110], [111]); of workgroup 0's post-processing, its four phases
+// (stats[106..109]), the parts of the running sums (stats[112..115]: dense copy, list apply, f64
+// update, the barrier after the apply) and the centre update's shift pass (stats[116]); from all
+// workgroups, the sparse item-sweeps whose list overflowed (stats[117]).
 #ifdef CC_KM_STAMPS
 #define KM_STAMP(var)                  \
   __builtin_amdgcn_sched_barrier(0);   \
@@ -575,6 +578,145 @@ __device__ void apply_changes(const KArgs& a, const int32_t* idx, const uint2* l
     }
   }
 }
+
+// ---- The element-wise passes of the post-sweep phase.  They are functions of their own, not
+// inlined (inlined, they moved the sweep loops' register allocation: spills 85 -> 133 at d = 128),
+// so their pointers say which memory they mean: inside an out-of-line function a plain pointer
+// is generic, and its loads would be flat ones that wait for LDS and global memory alike.
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+typedef double v2d __attribute__((ext_vector_type(2)));
+#define KM_GLOBAL __attribute__((address_space(1)))
+#define KM_LDS __attribute__((address_space(3)))
+template <class T>
+__device__ __forceinline__ T* as_lds(T* p) {
+  return (T*)(KM_LDS T*)p;
+}
+
+// A thread's slot of the element-wise centre passes: thread (slot tid / 2, half tid % 2) owns
+// the DP / 2 contiguous dims of its half row of Sm as float4s, so the slot's item, problem,
+// count and argmax are looked up once per thread, not once per element.  The float4s are walked
+// from a per-thread rotation, so that the threads' accesses, DP / 2 floats apart, fall into
+// different LDS banks.
+template <int DP>
+struct SlotHalf {
+  static constexpr int NQ = DP / 8;  // float4s per thread
+  bool run = false;                  // a slot of a RUN item
+  int p = 0, cl = 0, rot = 0;
+  KM_LDS v4f* row = nullptr;
+  template <class St>
+  __device__ __forceinline__ SlotHalf(float* Sm, const St& S, int ncols) {
+    const int tid = threadIdx.x, sl = tid >> 1;
+    rot = tid / (128 / DP);
+    row = (KM_LDS v4f*)(KM_LDS float*)Sm + (sl * DP + (tid & 1) * (DP / 2)) / 4;
+    if (sl < ncols) {
+      const int it = S.sitem[sl];
+      if (it >= 0 && S.ikind[it] == IK_RUN) {
+        run = true;
+        p = S.iprob[it];
+        cl = sl - S.ioff[it];
+      }
+    }
+  }
+  __device__ __forceinline__ int q(int j) const { return (j + rot) & (NQ - 1); }
+};
+
+// _average_centers (_k_means_common.pyx:215-237) runs j in order: an empty cluster j copies
+// centre argmax(weight), which is still a raw sum when j < argmax.  Ends without a barrier.
+template <int DP, class St>
+__device__ __noinline__ void average_centres(float* Sm_, St& S_, int ncols) {
+  float* Sm = as_lds(Sm_);
+  const St& S = *as_lds(&S_);
+  const SlotHalf<DP> h(Sm, S, ncols);
+  constexpr int NQ = SlotHalf<DP>::NQ;
+  const int am = h.run ? S.amax[h.p] : 0;
+  const unsigned cn = h.run ? S.cnt[threadIdx.x >> 1] : 1u;
+  const KM_LDS v4f* amrow = h.row + (am - h.cl) * (DP / 4);  // the same half of the argmax row
+  if (h.run && cn == 0 && h.cl <= am) {
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) h.row[h.q(j)] = amrow[h.q(j)];
+  }
+  __syncthreads();
+  if (h.run && cn > 0) {
+    const float alpha = static_cast<float>(1.0 / static_cast<double>(static_cast<float>(cn)));
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) h.row[h.q(j)] = h.row[h.q(j)] * alpha;
+  }
+  __syncthreads();
+  if (h.run && cn == 0 && h.cl >= am) {
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) h.row[h.q(j)] = amrow[h.q(j)];
+  }
+}
+
+// The new centres of the problems that sweep again, from Sm to cen.
+template <int DP, class St>
+__device__ __noinline__ void write_centres(float* Sm_, St& S_, float* cen, int ncols) {
+  float* Sm = as_lds(Sm_);
+  const St& S = *as_lds(&S_);
+  const SlotHalf<DP> h(Sm, S, ncols);
+  constexpr int NQ = SlotHalf<DP>::NQ;
+  if (h.run && S.st[h.p] != ST_DONE) {
+    KM_GLOBAL v4f* co = (KM_GLOBAL v4f*)reinterpret_cast<uintptr_t>(cen) +
+                        ((S.cenoff[h.p] + h.cl) * DP + (threadIdx.x & 1) * (DP / 2)) / 4;
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) co[h.q(j)] = h.row[h.q(j)];
+  }
+}
+
+// Sparse items (d = 128): f64 running sums += the f32 deltas in Sm, counts likewise; Sm and cnt
+// then hold the totals.  A wave takes 32 consecutive slots, eight at a time: a slot's item, row
+// and flags are looked up once (not once per element), a lane holds 2 of the row's 128 dims, and
+// the eight rows' running sums (1 KiB each, contiguous) are in flight together.  The arithmetic
+// per element is what it was: (rebuild ? 0.0 : sum) + delta.
+template <int DP, class St>
+__device__ __noinline__ void add_sparse_deltas(float* Sm_, St& S_, double* s64_, int* c64_, int ncols) {
+  static_assert(DP == 2 * 64, "a lane holds 2 dims");
+  KM_LDS v2f* Sm = (KM_LDS v2f*)(KM_LDS float*)Sm_;
+  St& S = *as_lds(&S_);
+  KM_GLOBAL v2d* s64 = (KM_GLOBAL v2d*)reinterpret_cast<uintptr_t>(s64_);
+  KM_GLOBAL int* c64 = (KM_GLOBAL int*)reinterpret_cast<uintptr_t>(c64_);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  ncols = __builtin_amdgcn_readfirstlane(ncols);
+  constexpr int U = 8, SPW = CW / NW;
+  for (int s0 = wave * SPW; s0 < min(ncols, (wave + 1) * SPW); s0 += U) {  // wave-uniform
+    v2d v[U];
+    int rowu[U], cu[U];
+    bool act[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int sl = s0 + u;
+      act[u] = false;
+      rowu[u] = cu[u] = 0;
+      v[u] = v2d{0.0, 0.0};  // with a rebuild the sums restart from 0.0
+      if (sl >= ncols) continue;
+      const int it = S.sitem[sl];  // < 0: a padding slot (cluster >= K)
+      if (it < 0 || S.ikind[it] != IK_RUN || !S.isparse[it]) continue;
+      act[u] = true;
+      rowu[u] = S.cenoff[S.iprob[it]] + (sl - S.ioff[it]);
+      if (!(S.ichanged[it] & 2u)) {
+        v[u] = s64[rowu[u] * (DP / 2) + lane];
+        cu[u] = c64[rowu[u]];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (!act[u]) continue;
+      const int sl = s0 + u;
+      const v2f f = Sm[sl * (DP / 2) + lane];
+      const v2d t = {v[u].x + static_cast<double>(f.x), v[u].y + static_cast<double>(f.y)};
+      s64[rowu[u] * (DP / 2) + lane] = t;
+      Sm[sl * (DP / 2) + lane] = v2f{static_cast<float>(t.x), static_cast<float>(t.y)};
+      if (lane == 0) {
+        const int c = cu[u] + static_cast<int>(S.cnt[sl]);
+        c64[rowu[u]] = c;
+        S.cnt[sl] = static_cast<unsigned>(c);
+      }
+    }
+  }
+}
+#undef KM_GLOBAL
+#undef KM_LDS
 
 // k-means++ candidate positions for centre S.c[p] (>= 1) of problem p, one wave, from the
 // problem's current closest-distance column (kmeans_shared.hpp).
@@ -1643,6 +1785,9 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
             }
             S.pchg[S.iprob[it]] = static_cast<int>(tot);
             S.ichanged[it] = (tot != 0) | ((S.isparse[it] && over) ? 2u : 0u);  // 2: rebuild the sums
+#ifdef CC_KM_STAMPS
+            if (S.isparse[it] && over && a.stats) atomicAdd(&a.stats[117], 1ull);  // rebuilds, all workgroups
+#endif
           }
         }
       } else {  // flags only, every item in one pass (set by any thread that sees a difference:
@@ -1678,6 +1823,7 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
           s64[static_cast<size_t>(row) * DP + d] = static_cast<double>(Sm[e]);
           if (d == 0) c64[row] = static_cast<int>(S.cnt[sl]);
         }
+        KM_STAMP(rs0);
         {
           int j = 0;
           for (int it = 0; it < nitems; ++it) {
@@ -1689,24 +1835,20 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
                               S.cnt + off, S.K[p], lane);
           }
         }
+        KM_STAMP(rs1);
         __syncthreads();
-        for (int e = tid; e < ncols * DP; e += NT) {  // sparse items: f64 sums += the f32 deltas
-          const int sl = e / DP, d = e - sl * DP;
-          const int it = S.sitem[sl];
-          if (it < 0 || S.ikind[it] != IK_RUN || !S.isparse[it] || sl - S.ioff[it] >= S.K[S.iprob[it]]) continue;
-          const int row = S.cenoff[S.iprob[it]] + (sl - S.ioff[it]);
-          const bool full = (S.ichanged[it] & 2u) != 0;
-          double* sp = s64 + static_cast<size_t>(row) * DP + d;
-          const double t = (full ? 0.0 : *sp) + static_cast<double>(Sm[e]);
-          *sp = t;
-          Sm[e] = static_cast<float>(t);
-          if (d == 0) {
-            const int c = (full ? 0 : c64[row]) + static_cast<int>(S.cnt[sl]);
-            c64[row] = c;
-            S.cnt[sl] = static_cast<unsigned>(c);
-          }
-        }
+        KM_STAMP(rs2);
+        add_sparse_deltas<DP>(Sm, S, s64, c64, ncols);
+        KM_STAMP(rs3);
         __syncthreads();
+#ifdef CC_KM_STAMPS
+        if (blockIdx.x == 0 && tid == 0 && a.stats) {  // running sums: dense copy, apply, f64 update
+          atomicAdd(&a.stats[112], rs0 - ppB);
+          atomicAdd(&a.stats[113], rs1 - rs0);
+          atomicAdd(&a.stats[114], rs3 - rs2);
+          atomicAdd(&a.stats[115], rs2 - rs1);  // the barrier after the apply (the one after the
+        }                                       // update: stats[108] less these four)
+#endif
       }
 
       KM_STAMP(ppC);
@@ -1750,35 +1892,10 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
       __syncthreads();
       // _average_centers (_k_means_common.pyx:215-237) runs j in order: an empty cluster
       // j copies centre argmax(weight), which is still a raw sum when j < argmax.
-      for (int e = tid; e < ncols * DP; e += NT) {
-        const int sl = e / DP, d = e - sl * DP;
-        const int it = S.sitem[sl];
-        if (it < 0 || S.ikind[it] != IK_RUN || S.cnt[sl] != 0) continue;
-        const int p = S.iprob[it], off = S.ioff[it];
-        if (sl - off > S.amax[p]) continue;
-        Sm[sl * DP + d] = Sm[(off + S.amax[p]) * DP + d];
-      }
-      __syncthreads();
-      for (int e = tid; e < ncols * DP; e += NT) {
-        const int sl = e / DP;
-        if (S.sitem[sl] < 0 || S.ikind[S.sitem[sl]] != IK_RUN) continue;
-        const unsigned cn = S.cnt[sl];
-        if (cn > 0) {
-          const float alpha = static_cast<float>(1.0 / static_cast<double>(static_cast<float>(cn)));
-          Sm[e] *= alpha;
-        }
-      }
-      __syncthreads();
-      for (int e = tid; e < ncols * DP; e += NT) {
-        const int sl = e / DP, d = e - sl * DP;
-        const int it = S.sitem[sl];
-        if (it < 0 || S.ikind[it] != IK_RUN || S.cnt[sl] != 0) continue;
-        const int p = S.iprob[it], off = S.ioff[it];
-        if (sl - off < S.amax[p]) continue;
-        Sm[sl * DP + d] = Sm[(off + S.amax[p]) * DP + d];
-      }
+      average_centres<DP>(Sm, S, ncols);
       __syncthreads();
       // centre shifts (sklearn _euclidean_dense_dense, 4-way unrolled f32)
+      KM_STAMP(cu0);
       if (tid < ncols && S.sitem[tid] >= 0 && S.ikind[S.sitem[tid]] == IK_RUN) {
         const int sl = tid;
         const int it = S.sitem[sl];
@@ -1800,6 +1917,7 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
         S.shift[sl] = sh * sh;
       }
       __syncthreads();
+      KM_STAMP(cu1);
       // convergence decisions (_kmeans_single_lloyd :697-736)
       if (tid < nitems && S.ikind[tid] >= IK_RUN) {
         const int it = tid, p = S.iprob[it];
@@ -1811,14 +1929,7 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
       }
       __syncthreads();
       // write back the centres (and norms) of problems that sweep again
-      for (int e = tid; e < ncols * DP; e += NT) {
-        const int sl = e / DP, d = e - sl * DP;
-        const int it = S.sitem[sl];
-        if (it < 0 || S.ikind[it] != IK_RUN) continue;
-        const int p = S.iprob[it];
-        if (S.st[p] == ST_DONE) continue;
-        cen[(S.cenoff[p] + (sl - S.ioff[it])) * DP + d] = Sm[e];
-      }
+      write_centres<DP>(Sm, S, cen, ncols);
       if (tid < ncols) {
         const int it = S.sitem[tid];
         if (it >= 0 && S.ikind[it] == IK_RUN) {
@@ -1836,6 +1947,7 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
         atomicAdd(&a.stats[107], ppB - ppA);
         atomicAdd(&a.stats[108], ppC - ppB);
         atomicAdd(&a.stats[109], pp1 - ppC);
+        atomicAdd(&a.stats[116], cu1 - cu0);  // of the centre update: the shift pass
       }
       // sweep cycles and counts by width (active 32-slot waves 1..8), all workgroups
       if (tid == 0 && a.stats) {
@@ -2133,6 +2245,13 @@ extern "C" int cc_kmeans_batched(const float* X, const uint16_t* Xhl, const floa
       e = hipMemcpyToSymbolAsync(HIP_SYMBOL(cc_km_share_seed), &share, sizeof(int), 0, hipMemcpyHostToDevice, st);
       if (e != hipSuccess) return hip_fail("cc_kmeans_batched", e);
       share_set = share;
+    }
+    // Diagnostics (CCMI_KM_LSEG=<entries>): a smaller change-list capacity per segment (a multiple
+    // of 16 in [16, list_seg(m)]; the workspace keeps its size), so that a small problem reaches
+    // the overflow -> rebuild path of the sparse M-step.
+    if (const char* ls = std::getenv("CCMI_KM_LSEG")) {
+      const long v = std::strtol(ls, nullptr, 10);
+      if (v > 0) a.lseg = static_cast<int>(std::min<long>(L.lseg, std::max<long>(16, v & ~15L)));
     }
   }
   const unsigned blocks = static_cast<unsigned>(std::min<long long>(grid, static_cast<long long>(nh) * nU));

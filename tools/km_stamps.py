@@ -43,3 +43,8 @@ print("sweeps with seeding items: %d of %d, %.1f%% of the sweep cycles; seeding 
 pp = st[106:110] / 1e6
 print("post-processing phases (wg0, Mcycles): seeding %.1f, label compare %.1f, running sums %.1f, centre update %.1f"
       % tuple(pp))
+rs = st[112:116] / 1e6
+print("  running sums: dense copy %.1f, list apply %.1f, f64 update %.1f, barrier after the apply %.1f, "
+      "barrier after the update %.1f" % (rs[0], rs[1], rs[2], rs[3], pp[2] - rs.sum()))
+print("  centre update: shift pass %.1f, the rest %.1f" % (st[116] / 1e6, pp[3] - st[116] / 1e6))
+print("sparse item-sweeps %d (%d of them rebuilt after a list overflow), label changes %d" % (st[6], st[117], st[7]))
