@@ -224,9 +224,9 @@ extern "C" size_t cc_kmeans_fit_workspace_bytes(int n, int d, int m, int nh, con
     const int g = std::min(P.cus, nh * P.nU);
     engine = cc_kmeans_workspace_bytes(m, P.dpad, P.units.data(), P.nU, P.seedmax, g);
   } else {
-    const int per_call = std::max(1, CC_KM_PMAX / n_init);
-    for (int k0 = 0; k0 < nK; k0 += per_call) {
-      const int nk = std::min(per_call, nK - k0);
+    for (int k0 = 0, nk; k0 < nK; k0 += nk) {  // the calls cc_kmeans_fit makes
+      nk = cc_kmeans_wide_chunk(m, P.dpad, Ks + k0, nK - k0, n_init);
+      if (nk <= 0) return 0;
       engine = std::max(engine, cc_kmeans_wide_workspace_bytes(m, P.dpad, Ks + k0, nk, n_init, std::min(nh, 128)));
     }
   }
@@ -340,11 +340,12 @@ extern "C" int cc_kmeans_fit(const void* X, int n, int d, const int32_t* idx_hm,
                              ldl, static_cast<float*>(inertia), n_iter, stats, w + off, ws_bytes - off, g,
                              P.seedmax, stream);
   }
-  // wide rows: rounds over batches of resamples sized to the workspace, <= CC_KM_PMAX problems
-  // per call
-  const int per_call = std::max(1, CC_KM_PMAX / n_init);
-  for (int k0 = 0; k0 < nK; k0 += per_call) {
-    const int nk = std::min(per_call, nK - k0);
+  // wide rows: rounds over batches of resamples sized to the workspace; each call takes the K
+  // values cc_kmeans_wide_chunk gives it (<= CC_KM_PMAX problems, within the engine's centroid
+  // capacity).  A K that fits no call alone is that function's error, which names K and n_init.
+  for (int k0 = 0, nk; k0 < nK; k0 += nk) {
+    nk = cc_kmeans_wide_chunk(m, P.dpad, Ks + k0, nK - k0, n_init);
+    if (nk <= 0) return nk;
     const size_t w1 = cc_kmeans_wide_workspace_bytes(m, P.dpad, Ks + k0, nk, n_init, 1);
     const size_t w2 = cc_kmeans_wide_workspace_bytes(m, P.dpad, Ks + k0, nk, n_init, 2);
     if (w1 == 0 || off + w1 > ws_bytes) {

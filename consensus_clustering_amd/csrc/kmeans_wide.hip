@@ -1235,6 +1235,30 @@ extern "C" size_t cc_kmeans_wide_workspace_bytes(int m, int dpad, const int32_t*
   return HDR + L.per * static_cast<size_t>(batch);
 }
 
+// How callers split a K list into cc_kmeans_wide calls (BatchedKMeans._run_wide, cc_kmeans_fit
+// and cc_kmeans_fit_workspace_bytes all ask here, so they cannot drift apart): the longest prefix
+// of Ks that wide_layout accepts.  Every quantity wide_layout bounds grows with the prefix, so
+// the first prefix that fails ends the search.
+extern "C" int cc_kmeans_wide_chunk(int m, int dpad, const int32_t* Ks, int nK, int n_init) {
+  if (m <= 0 || dpad <= 0 || !Ks || nK <= 0 || n_init <= 0) {
+    cc::set_error("cc_kmeans_wide_chunk: bad arguments");
+    return CC_ERR_ARG;
+  }
+  int nk = 0;
+  for (; nk < nK; ++nk) {
+    WL L;
+    if (!wide_layout(m, dpad, Ks, nk + 1, n_init, L)) break;
+  }
+  if (nk == 0) {
+    if (Ks[0] >= 1 && Ks[0] <= KMAX && Ks[0] <= m)  // otherwise wide_layout's message names the range
+      cc::set_error("cc_kmeans_wide: K = " + std::to_string(Ks[0]) + " with n_init = " + std::to_string(n_init) +
+                    " does not fit one call (at most " + std::to_string(PMAX) + " (K, init) problems in " +
+                    std::to_string(CTMAX) + " column tiles of " + std::to_string(CWW) + " centroid slots)");
+    return CC_ERR_UNSUPPORTED;
+  }
+  return nk;
+}
+
 extern "C" int cc_kmeans_wide(const float* X, const uint16_t* Xhl, const float* xnorm, int n, int dreal,
                               int dpad, int scale_exp, const int32_t* idx_hm, int H, int m, int h_begin,
                               int h_end, const int32_t* Ks, int nK, int n_init, int max_iter, double tol_rel,

@@ -170,6 +170,7 @@ class BatchedKMeans:
         self.wide_budget = int(wide_budget)
         self.stats = None
         self.units = None
+        self.wide_calls = None
 
     def run(self, Xd, xnorm, dreal, idx_d, n, H, m, h_begin, h_end, labels_nh, weight_dtype,
             inertia=None, n_iter=None, Xhl=None, scale_exp=None):
@@ -267,19 +268,28 @@ class BatchedKMeans:
 
     def _run_wide(self, Xd, xnorm, dreal, idx_d, n, H, m, h_begin, h_end, labels_nh, weight_dtype,
                   inertia, n_iter, Xhl, scale_exp):
-        """d > 128: cc_kmeans_wide over batches of resamples sized to the workspace budget,
-        at most 64 (K, init) problems per call."""
+        """d > 128: cc_kmeans_wide over batches of resamples sized to the workspace budget.  Each
+        call takes the next K values in K_range order that fit it (cc_kmeans_wide_chunk: at most
+        64 (K, init) problems within the engine's centroid capacity, the rule cc_kmeans_fit
+        follows too); a K that fits no call alone raises, naming K and n_init."""
         dev = Xd.device
         lib = _lib.load()
         dpad = Xd.shape[1]
         nh = h_end - h_begin
-        per_call = max(1, 64 // self.n_init)
         free = torch.cuda.mem_get_info(dev)[0]
         budget = min(self.wide_budget, int(0.6 * free))
         ldl = labels_nh.stride(1)
-        for k0 in range(0, len(self.Ks), per_call):
+        all_Ks = np.ascontiguousarray(np.asarray(self.Ks, dtype=np.int32))
+        self.wide_calls = []  # the K values of each cc_kmeans_wide call
+        k0 = per_call = 0
+        while k0 + per_call < len(self.Ks):
+            k0 += per_call
+            per_call = lib.cc_kmeans_wide_chunk(m, dpad, all_Ks[k0:].ctypes.data, len(self.Ks) - k0, self.n_init)
+            if per_call <= 0:
+                _lib.check(per_call or -1, "cc_kmeans_wide_chunk")
             Ks = self.Ks[k0:k0 + per_call]
-            Ks_np = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
+            self.wide_calls.append(Ks)
+            Ks_np = np.ascontiguousarray(all_Ks[k0:k0 + per_call])
             ws1 = lib.cc_kmeans_wide_workspace_bytes(m, dpad, Ks_np.ctypes.data, len(Ks),
                                                      self.n_init, 1)
             ws2 = lib.cc_kmeans_wide_workspace_bytes(m, dpad, Ks_np.ctypes.data, len(Ks),

@@ -323,6 +323,12 @@ int cc_kmeans_batched(const float* X, const uint16_t* Xhl, const float* xnorm, i
  * resample-rounds and stats[5] 256-slot column tiles x rounds. */
 size_t cc_kmeans_wide_workspace_bytes(int m, int dpad, const int32_t* Ks, int nK, int n_init,
                                       int batch);
+/* How to split a K list over cc_kmeans_wide calls: the number (>= 1) of leading values of
+ * Ks [nK] that one call takes, the most that keep nK * n_init <= CC_KM_PMAX and fit the
+ * engine's centroid capacity (8 column tiles of 256 slots; a K takes n_init * (K rounded up to
+ * 4) of them and one tile is kept as packing slack).  Call it again on the rest.  Negative (an error naming K and n_init) when
+ * Ks[0] fits no call on its own. */
+int cc_kmeans_wide_chunk(int m, int dpad, const int32_t* Ks, int nK, int n_init);
 
 int cc_kmeans_wide(const float* X, const uint16_t* Xhl, const float* xnorm, int n, int dreal,
                    int dpad, int scale_exp, const int32_t* idx_hm, int H, int m, int h_begin,

@@ -78,6 +78,9 @@ def _expr(n, d, seed, groups=5):
     return make_expression_f32(n, d, groups=groups, seed=seed)
 
 
+# one K on each side of every K threshold of the engines (DESIGN.md "K thresholds")
+BIGK = [21, 24, 25, 32, 33, 54, 55, 64, 65, 96, 97, 125, 127]
+
 # Each case mirrors one GPU test's data exactly (the test asserts the X digest):
 #   X(), Ks, seed, frac, classify = resamples checked with sk_parity, ref = identity-only resamples
 CASES = {
@@ -101,6 +104,28 @@ CASES = {
     "c4_full": dict(X=lambda: _expr(5_000, 20_000, 0), Ks=list(range(2, 13)), seed=0, classify=[0]),
     # C5 (n = 200 000, m = 160 000, d = 32, K = 2..10): the d = 32 pair-mode engine at its real m
     "c5_full": dict(X=lambda: _blobs(200_000, 32, 6, 0), Ks=list(range(2, 11)), seed=0, classify=[0, 1]),
+    # tests/test_gpu_kmeans_bigk.py: K above 20 on 128 tight blobs (std 0.3, seed n + d), where
+    # sklearn's own fit shows no rounding sensitivity, so every (K, h) is checked for identity.
+    # Resample 0 carries the full evidence, the others are identity-only digests.  The data seed
+    # is n + d + 1000 j with the first j = 0, 1, ... at which every resample-0 problem of the case
+    # has reasons == 0: j = 4, 0, 5 for d = 16, 40, 100, 3 on wide rows, 29 for K = 2..30 at d = 16
+    # (merging 128 blobs into few clusters passes a near tie in about one problem of ten).  On
+    # wide rows K = 2..30 found no such j in 0..59 (1 to 9 problems of 29 each time), so
+    # range_n1024_d300 keeps j = 0: K = 16 and K = 24 pass one near tie each on resample 0 (bit 64,
+    # no perturbation moves the labels), the one resample the test also puts through sk_parity's
+    # classification.
+    "bigk_n1536_d16": dict(X=lambda: _blobs(1536, 16, 128, 4552, std=0.3), Ks=BIGK, seed=7, classify=[0], ref=[1, 2]),
+    "bigk_n1536_d40": dict(X=lambda: _blobs(1536, 40, 128, 1576, std=0.3), Ks=BIGK, seed=7, classify=[0], ref=[1, 2]),
+    "bigk_n1536_d100": dict(X=lambda: _blobs(1536, 100, 128, 5636, std=0.3), Ks=BIGK, seed=7, classify=[0],
+                            ref=[1, 2]),
+    "bigk_n1024_d300": dict(X=lambda: _blobs(1024, 300, 128, 4324, std=0.3), Ks=BIGK, seed=7, classify=[0], ref=[1]),
+    "bigk5_n1024_d300": dict(X=lambda: _blobs(1024, 300, 128, 4324, std=0.3), Ks=[21, 25, 33, 55, 127], seed=7,
+                             classify=[0], ref=[1]),
+    # more than 21 K values (64 // n_init): several units (narrow) and several calls (wide)
+    "range_n1536_d16": dict(X=lambda: _blobs(1536, 16, 128, 29552, std=0.3), Ks=list(range(2, 31)), seed=7,
+                            classify=[0], ref=[1, 2]),
+    "range_n1024_d300": dict(X=lambda: _blobs(1024, 300, 128, 1324, std=0.3), Ks=list(range(2, 31)), seed=7,
+                             classify=[0], ref=[1]),
 }
 def _f64_noisy(n, d, k):
     """tests/test_gpu_kmeans.py::test_f64_labels_match_sklearn_float64's rows: blobs at seed n + d
@@ -116,6 +141,12 @@ F64_SMALL = {
     "f64_n29_d29": dict(X=lambda: _f64_noisy(29, 29, 3), Ks=[2, 3, 4, 5, 6, 7, 8, 9, 10], seed=3, H=6),
     "f64_n600_d12": dict(X=lambda: _f64_noisy(600, 12, 4), Ks=[2, 3, 4, 6, 9], seed=3, H=4),
     "f64_n300_d150": dict(X=lambda: _f64_noisy(300, 150, 3), Ks=[2, 3, 5], seed=3, H=3),
+    # tests/test_gpu_kmeans_bigk.py::test_f64_bigk_identical_to_sklearn_float64: 128 blobs, m = 320 rows,
+    # K up to 127 (7 full 16-centre tiles and one of 15).  Empty clusters are relocated here, so
+    # sklearn's side is generated under the engine's documented order among tied farthest rows
+    # (lowest index first, _fit_lowest_index) and compared with numpy's own order.
+    "f64_n400_d24": dict(X=lambda: _f64_noisy(400, 24, 128), Ks=[21, 33, 55, 100, 127], seed=3, H=2, rule=True),
+    "f64_n400_d150": dict(X=lambda: _f64_noisy(400, 150, 128), Ks=[21, 33, 55, 100, 127], seed=3, H=2, rule=True),
 }
 F64_CASE = dict(X=lambda: _blobs(50_000, 128, 8, 5, dtype=np.float64), Ks=list(range(2, 21)), seed=0, H=2)
 PAC_CASES = {
@@ -138,6 +169,50 @@ def _fit(rows, K, seed, threads=1):
     with threadpool_limits(threads):
         km = KMeans(n_clusters=K, random_state=seed, n_init=3).fit(rows)
     return km.labels_.astype(np.int8), int(km.n_iter_), float(km.inertia_)
+
+
+class _LowestIndexFirst:
+    """numpy whose argpartition(distances, -k)[:-k-1:-1] is the k farthest rows, farthest first and
+    the lowest index first among equal distances (cc_kmeans_f64's documented relocation order;
+    numpy leaves the order among ties to its partition algorithm).  Counts the relocated rows."""
+
+    def __init__(self):
+        self.relocated = 0
+
+    def __getattr__(self, k):
+        return getattr(np, k)
+
+    def argpartition(self, a, kth, *args, **kw):
+        a = np.asarray(a)
+        ne = -int(kth)
+        self.relocated += ne
+        order = np.lexsort((np.arange(len(a)), -a))  # farthest first, lowest index on ties
+        top = order[:ne]
+        rest = np.setdiff1d(np.arange(len(a)), top)
+        return np.concatenate([rest, top[::-1]])
+
+
+def _fit_lowest_index(rows, K, seed):
+    """_fit with sklearn's empty-cluster relocation (_k_means_common.pyx) under _LowestIndexFirst.
+    Returns _fit's triple, the number of relocated rows over the three inits, and whether numpy's
+    own order gives the same labels."""
+    import sklearn.cluster._k_means_common as kmc
+
+    real = _fit(rows, K, seed)
+    rule = _LowestIndexFirst()
+    kmc.np = rule
+    try:
+        lab, nit, inert = _fit(rows, K, seed)
+    finally:
+        kmc.np = np
+    return lab, nit, inert, rule.relocated, bool(np.array_equal(real[0], lab) and real[1] == nit)
+
+
+def _rule_task(args):
+    case, K, h = args
+    X, spec = _X[case], F64_SMALL[case]
+    rows = X[indices(X.shape[0], spec["seed"], h)]
+    return (case, K, h) + _fit_lowest_index(rows.astype(np.float64), K, spec["seed"])
 
 
 def _classify_task(args):
@@ -322,20 +397,35 @@ def make_f64(ex, case="f64_c3shape"):
     X = _X[case]
     Ks, H = spec["Ks"], spec["H"]
     t0 = time.time()
-    res = list(ex.map(_ref_task, [(case, K, h, np.float64) for K in Ks for h in range(H)]))
+    rule = bool(spec.get("rule"))
+    task = _rule_task if rule else _ref_task
+    res = list(ex.map(task, [(case, K, h) + (() if rule else (np.float64,)) for K in Ks for h in range(H)]))
     dig = np.full((len(Ks), H), "", dtype="U64")
     nit = np.zeros((len(Ks), H), dtype=np.int32)
     inert = np.zeros((len(Ks), H), dtype=np.float64)
-    for (_, K, h, lab, it, ine) in res:
+    reloc = np.zeros((len(Ks), H), dtype=np.int32)
+    as_numpy = np.ones((len(Ks), H), dtype=bool)
+    for (_, K, h, lab, it, ine, *more) in res:
         k = Ks.index(K)
         dig[k, h], nit[k, h], inert[k, h] = digest(lab), it, ine
+        if more:
+            reloc[k, h], as_numpy[k, h] = more
     note = ("make_blobs(50000, 128, 8 centers, std 1, box (-10, 10), seed 5) float64"
             if case == "f64_c3shape" else "tests/test_gpu_kmeans.py blobs + N(0, 0.5^2) noise")
     meta = dict(kind="f64", case=case, n=X.shape[0], d=X.shape[1], Ks=Ks, seed=spec["seed"], frac=0.8,
                 H=H, x_sha256=digest(X), note=note + "; sklearn KMeans(n_init=3) float64, 1 thread")
+    extra = {}
+    if rule:
+        meta["relocation_rule"] = ("sklearn's relocation with the farthest rows taken lowest index first among "
+                                   "equal distances (cc_kmeans_f64's order)")
+        meta["relocated_rows"] = int(reloc.sum())
+        meta["problems_where_numpy_order_differs"] = int((~as_numpy).sum())
+        extra = dict(relocated=reloc, same_as_numpy_order=as_numpy)
     np.savez_compressed(os.path.join(OUT, f"{case}.npz"), digest64=dig, n_iter=nit, inertia=inert,
-                        meta=np.array(json.dumps(meta)))
-    print(f"{case}: {len(res)} fits ({time.time() - t0:.0f} s); n_iter {nit.min()}..{nit.max()}", flush=True)
+                        meta=np.array(json.dumps(meta)), **extra)
+    print(f"{case}: {len(res)} fits ({time.time() - t0:.0f} s); n_iter {nit.min()}..{nit.max()}"
+          + (f"; relocated rows {reloc.sum()} in {int((reloc > 0).sum())} problems, numpy's tie order differs "
+             f"in {int((~as_numpy).sum())}" if rule else ""), flush=True)
 
 
 PAC_NUDGES = 2  # extra reference runs per PAC case: the float32 fit on 2^-22-nudged inputs

@@ -54,3 +54,11 @@ def test_single_resample_and_tiny_n():
 def test_uint16_counts_just_above_uint8():
     cc = _check(_blobs(120, 4, 2, seed=6), [2], 256)
     assert cc.cdf_at_K_data[2]["mij"].dtype == np.uint16
+
+
+def test_k127_end_to_end():
+    """K_range up to KMAX = 127 through the drop-in fit: 128 tight blobs, so the co-association
+    at K = 127 runs on real 127-cluster labels; M, the histogram and the PAC area equal the
+    oracle's."""
+    cc = _check(_blobs(600, 8, 128, seed=608, std=0.3), [2, 30, 127], 8)
+    assert cc.cdf_at_K_data[127]["mij"].shape == (600, 600)

@@ -13,6 +13,9 @@ from consensus_clustering_amd.kmeans import BatchedKMeans, prepare_rows
 pytestmark = pytest.mark.gpu
 
 
+BIGK = [21, 24, 25, 32, 33, 54, 55, 64, 65, 96, 97, 125, 127]
+
+
 def _blobs(n, d, k, seed, dtype):
     rng = np.random.default_rng(seed)
     C = rng.uniform(-6, 6, size=(k, d))
@@ -61,6 +64,10 @@ def _fit_host(X, Ks, H, m, h0, h1, idx_d, precision, seed=3):
     (2000, 128, [3, 8], 9, 2, 7, 0),              # a shard of the resamples
     (600, 300, [2, 4, 7], 5, 0, 5, 0),            # cc_kmeans_wide
     (400, 12, [2, 3, 6], 6, 1, 6, 1),             # cc_kmeans_f64
+    # one K on each side of every K threshold (tests/test_gpu_kmeans_bigk.py); on wide rows the
+    # list needs several cc_kmeans_wide calls, which both sides split by cc_kmeans_wide_chunk
+    (1536, 16, BIGK, 3, 0, 3, 0),
+    (1024, 300, BIGK, 2, 0, 2, 0),
 ])
 def test_one_call_matches_advanced_api(n, d, Ks, H, h0, h1, precision):
     dev = engine.require_gpu()

@@ -78,6 +78,9 @@ def test_alone_against_in_range(d):
     ([2, 3, 4, 5, 8, 9, 12], 3, 32, 1),
     ([2, 3, 4, 5, 6, 7, 8, 9, 12], 3, None, 2),  # classes split over units
     ([2, 3, 4, 5, 6, 7, 8, 9, 12], 3, None, 3),
+    ([21, 30, 54], 3, None, 1),        # inside trial class 5 (K = 21..54): 54 leads
+    ([55, 90, 127], 3, None, 1),       # inside trial class 6 = TMAX (K >= 55): 127 leads
+    ([20, 21, 54, 55], 3, None, 1),    # across both class boundaries: leaders 20, 54, 55
 ])
 def test_switch_on_against_off(monkeypatch, d, Ks, n_init, seedmax, nsub):
     monkeypatch.setenv("CCMI_NSUB", str(nsub))

@@ -6,7 +6,11 @@ from consensus_clustering_amd import kmeans
 
 
 @pytest.mark.parametrize("K,m,seed,dtype", [(2, 300, 0, np.float32), (7, 1000, 23, np.float32),
-                                            (20, 4000, 5, np.float64)])
+                                            (20, 4000, 5, np.float64),
+                                            # 2 + floor(ln K) = 5 trials (K = 21..54) and 6 (K >= 55)
+                                            (21, 400, 7, np.float32), (21, 400, 7, np.float64),
+                                            (55, 400, 7, np.float32), (55, 400, 7, np.float64),
+                                            (127, 400, 7, np.float32), (127, 400, 7, np.float64)])
 def test_kpp_stream_matches_sklearn(K, m, seed, dtype):
     from sklearn.cluster._kmeans import _kmeans_plusplus
 
@@ -51,6 +55,69 @@ def test_plan_splits_beyond_unit_capacity():
     Ks = list(range(2, 40))  # 38 K x 3 inits = 114 problems > 64 per unit
     g = kmeans.plan(Ks, 3, 1)
     assert len(g) == 2 and g[:, 0].sum() == 114
+
+
+@pytest.mark.parametrize("n_sub", [1, 2, 3, 7])
+def test_plan_mixes_k127_with_small_k(n_sub):
+    """K = 127 (a 128-slot item, 6 trials) among small K values: every (K, init) appears once, no
+    unit holds more than 64 problems, and each problem's trial count is 2 + floor(ln K), 6 at most
+    (TMAX)."""
+    Ks = [2, 127, 3, 21, 55, 126, 5, 125, 54, 20, 127, 8, 96, 4, 33, 7, 64, 6, 97, 12, 25, 9, 127, 10, 11]
+    g = kmeans.plan(Ks, 3, n_sub)
+    assert len(g) >= max(n_sub, 2)  # 75 problems never fit one unit
+    seen = []
+    for row in g:
+        P = row[0]
+        assert 0 < P <= 64
+        for p in range(P):
+            K, kidx, init, ntr = row[1 + 4 * p: 5 + 4 * p]
+            assert Ks[kidx] == K
+            assert ntr == kmeans.local_trials(K) and 2 <= ntr <= 6
+            seen.append((kidx, init))
+    assert sorted(seen) == [(k, i) for k in range(len(Ks)) for i in range(3)]
+    assert {kmeans.local_trials(K) for K in Ks} == {2, 3, 4, 5, 6}
+
+
+def test_wide_chunks_follow_the_engine_capacity():
+    """cc_kmeans_wide_chunk, the one rule by which BatchedKMeans._run_wide, cc_kmeans_fit and
+    cc_kmeans_fit_workspace_bytes split a K list over cc_kmeans_wide calls: K values in order
+    while the call has at most 64 // n_init of them and cc_kmeans_wide_workspace_bytes accepts it;
+    a K that fits no call alone is an error that names K and n_init."""
+    from consensus_clustering_amd import _lib
+
+    lib = _lib.load()
+    m, dpad = 819, 320
+
+    def chunks(Ks, n_init):
+        a = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
+        out, k0 = [], 0
+        while k0 < len(Ks):
+            nk = lib.cc_kmeans_wide_chunk(m, dpad, a[k0:].ctypes.data, len(Ks) - k0, n_init)
+            _lib.check(min(nk, 0), "cc_kmeans_wide_chunk")
+            out.append(Ks[k0:k0 + nk])
+            k0 += nk
+        return out
+
+    def fits(Ks, n_init):
+        a = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
+        return len(Ks) * n_init <= 64 and lib.cc_kmeans_wide_workspace_bytes(m, dpad, a.ctypes.data, len(Ks), n_init, 1) > 0
+
+    bigk = [21, 24, 25, 32, 33, 54, 55, 64, 65, 96, 97, 125, 127]
+    for Ks, n_init in ((list(range(2, 31)), 3), (bigk, 3), (bigk[::-1], 3), (bigk, 1), (list(range(2, 128)), 1),
+                       ([127] * 9, 5), (list(range(2, 13)), 3)):
+        got = chunks(Ks, n_init)
+        assert [K for c in got for K in c] == Ks
+        for i, c in enumerate(got):
+            assert fits(c, n_init), (c, n_init)
+            if i + 1 < len(got):  # greedy: the next K would not have fitted
+                assert not fits(c + got[i + 1][:1], n_init), (c, got[i + 1][:1], n_init)
+    assert chunks(list(range(2, 31)), 3) == [list(range(2, 23)), list(range(23, 31))]  # 21 = 64 // 3 K values
+    assert chunks(list(range(2, 13)), 3) == [list(range(2, 13))]
+    assert len(chunks(bigk, 3)) >= 2
+    a = np.asarray([127, 2], dtype=np.int32)
+    assert lib.cc_kmeans_wide_chunk(m, dpad, a.ctypes.data, 2, 16) < 0
+    msg = lib.cc_last_error().decode()
+    assert "K = 127" in msg and "n_init = 16" in msg and "workspace" not in msg
 
 
 def test_plan_rejects_unsupported():
