@@ -138,12 +138,21 @@ __host__ __device__ constexpr int dist_cost() { return KM_COST_DIST_NARROW; }
 
 // Diagnostic build only (-DCC_KM_STAMPS): per-wave cycle accounting of the sweep phases of
 // workgroup 0, added into stats[8 + 8 * wave + k] (k: issue, dist, estep, mstep, commit,
-// barrier) and stats[72..75] (sweep prologue, post-processing, unit setup, output); from all
+// barrier, sweep prologue) and stats[73..75] (post-processing, unit setup, output); from all
 // workgroups, sweep cycles and counts by width (stats[80..], [96..]) and of the sweeps that
 // carry seeding items (stats[110], [111]); of workgroup 0's post-processing, its four phases
 // (stats[106..109]), the parts of the running sums (stats[112..115]: dense copy, list apply, f64
 // update, the barrier after the apply) and the centre update's shift pass (stats[116]); from all
-// workgroups, the sparse item-sweeps whose list overflowed (stats[117]).
+// workgroups, the sparse item-sweeps whose list overflowed (stats[117]); of workgroup 0, the
+// scheduler's part of the sweep prologue (stats[118], from the sweep's start to the scheduling
+// wave's arrival at the barrier after it), of the unit setup its tol passes and its label fill
+// (stats[119], [120]), and the post-processing sections that one thread per problem or item runs
+// (stats[121]: releasing the seeding slots, the empty-cluster count, the label-buffer flip).
+// stats[0..7] are the engine's counters (every build): Lloyd column-rows, seeding column-rows,
+// M-step rows, relocations, sweeps, slot tiles, sparse item-sweeps, label changes.
+// Diagnostic build -DCC_KM_SCHED_CHECK (tools/km_sched_check.py): every sweep the serial reference
+// scheduler runs on a copy of the state in the workgroup's workspace, and stats[122] counts the
+// 32-bit words of the two states that differ (stats[123]: the sweeps compared).
 #ifdef CC_KM_STAMPS
 #define KM_STAMP(var)                  \
   __builtin_amdgcn_sched_barrier(0);   \
@@ -185,6 +194,9 @@ struct KArgs {
   int Pws, Kws, Tws, seedmax;
   int lsm;   // glab row stride (m rounded up to 64)
   int lseg;  // change-list entries per problem and wave segment
+#ifdef CC_KM_SCHED_CHECK
+  size_t off_chk;  // the serial reference scheduler's copy of the State
+#endif
 };
 
 // Diagnostics (CCMI_KM_DENSE=1 at launch): every Lloyd item runs the dense M-step, for the
@@ -445,48 +457,95 @@ __device__ void relocate(const KArgs& a, const int32_t* idx, int p, int off, con
                             S.n_reloc, tid);
 }
 
-// Wave w's part of the post-sweep label compare of a sparse item: rows [w * seg, (w + 1) * seg)
-// (seg = m / 8 rounded up to 16), 16 rows per lane and load; each changed row is appended to the
-// wave's segment of the item's change list as (row, old | new << 8), in row order (wave prefix
-// sum of the lanes' counts).  Returns the segment's count (it may exceed the capacity `cap`:
-// then only the count is meaningful).
-__device__ unsigned list_changes(const uint8_t* cur, const uint8_t* old, int m, int w, int lane, uint2* seg,
-                                 unsigned cap) {
+// Pointers that say which memory they mean, for the out-of-line (__noinline__) functions of the
+// scheduling and post-sweep code: inside such a function a plain pointer is generic, and its
+// loads would be flat ones that wait for LDS and global memory alike.
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+typedef double v2d __attribute__((ext_vector_type(2)));
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
+#define KM_GLOBAL __attribute__((address_space(1)))
+#define KM_LDS __attribute__((address_space(3)))
+template <class T>
+__device__ __forceinline__ T* as_lds(T* p) {
+  return (T*)(KM_LDS T*)p;
+}
+template <class T>
+__device__ __forceinline__ KM_GLOBAL T* as_global(T* p) {
+  return (KM_GLOBAL T*)reinterpret_cast<uintptr_t>(p);
+}
+
+// Wave w's part of the post-sweep label compare of a RUN item: rows [w * seg, (w + 1) * seg)
+// (seg = m / 8 rounded up to 16), 16 rows per lane and load, 1024 rows per wave and batch.  The
+// loads of KM_CMP_NB batches (at C3 a whole segment: 5) are issued before the first is consumed,
+// so the segment pays one global round trip, not one per batch.  A dense item (cap == 0) only
+// counts its changed rows (per lane, one wave sum at the end).  For a sparse item each changed
+// row is appended to the wave's segment of the item's change list as (row, old | new << 8), in
+// row order (wave prefix sum of the lanes' counts); a batch without a changed row (wave-uniform
+// ballot) skips the scan and the writes.  Returns the segment's count (it may exceed the
+// capacity `cap`: then only the count is meaningful).
+#ifndef KM_CMP_NB
+#define KM_CMP_NB 6
+#endif
+__device__ __noinline__ unsigned list_changes(const uint8_t* cur_, const uint8_t* old_, int m, int w, int lane,
+                                              uint2* seg_, unsigned cap) {
+  const KM_GLOBAL uint8_t* cur = as_global(cur_);
+  const KM_GLOBAL uint8_t* old = as_global(old_);
+  KM_GLOBAL v2u* seg = (KM_GLOBAL v2u*)reinterpret_cast<uintptr_t>(seg_);
+  constexpr int NB = KM_CMP_NB, BR = 16 * 64;
   const int rs = (((m + NW - 1) / NW) + 15) & ~15;
   const int r0 = w * rs, r1 = min(m, r0 + rs);
-  unsigned n = 0;
-  for (int b = r0; b < r1; b += 16 * 64) {  // wave-uniform
-    const int r = b + 16 * lane;
-    unsigned msk = 0;
-    uint4 x = make_uint4(0, 0, 0, 0), y = x;
-    if (r < r1) {  // r1 - r is a multiple of 16 except at m (rows past m hold 0xFF in both buffers)
-      x = *reinterpret_cast<const uint4*>(cur + r);
-      y = *reinterpret_cast<const uint4*>(old + r);
-      const unsigned xs[4] = {x.x, x.y, x.z, x.w}, ys[4] = {y.x, y.y, y.z, y.w};
+  unsigned n = 0, cl = 0;
+  for (int b0 = r0; b0 < r1; b0 += NB * BR) {  // wave-uniform
+    v4u x[NB], y[NB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {  // every batch's loads in flight together
+      const int r = b0 + u * BR + 16 * lane;
+      x[u] = y[u] = v4u{0u, 0u, 0u, 0u};
+      if (r < r1) {  // r1 - r is a multiple of 16 except at m (rows past m hold 0xFF in both buffers)
+        x[u] = *reinterpret_cast<const KM_GLOBAL v4u*>(cur + r);
+        y[u] = *reinterpret_cast<const KM_GLOBAL v4u*>(old + r);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+      if (b0 + u * BR >= r1) break;  // wave-uniform
+      const int r = b0 + u * BR + 16 * lane;
+      unsigned msk = 0;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const unsigned dq = xs[q] ^ ys[q];
+        const unsigned dq = x[u][q] ^ y[u][q];
 #pragma unroll
         for (int k = 0; k < 4; ++k) msk |= ((dq >> (8 * k)) & 0xFFu) ? (1u << (4 * q + k)) : 0u;
       }
-    }
-    const unsigned c = __popc(msk);
-    unsigned pre = c;  // inclusive wave scan of the counts
+      const unsigned c = __popc(msk);
+      if (cap == 0u) {  // wave-uniform: a dense item
+        cl += c;
+        continue;
+      }
+      if (__ballot(msk != 0u) == 0ull) continue;  // wave-uniform: nothing changed in this batch
+      unsigned pre = c;  // inclusive wave scan of the counts
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_up(pre, o);
-      if (lane >= o) pre += t;
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_up(pre, o);
+        if (lane >= o) pre += t;
+      }
+      unsigned pos = n + pre - c;
+      while (msk) {
+        const int k = __builtin_ctz(msk);
+        msk &= msk - 1;
+        const unsigned nv = (x[u][k >> 2] >> (8 * (k & 3))) & 0xFFu, ov = (y[u][k >> 2] >> (8 * (k & 3))) & 0xFFu;
+        if (pos < cap) seg[pos] = v2u{static_cast<unsigned>(r + k), ov | (nv << 8)};
+        ++pos;
+      }
+      n += __shfl(pre, 63);
     }
-    unsigned pos = n + pre - c;
-    const unsigned xs[4] = {x.x, x.y, x.z, x.w}, ys[4] = {y.x, y.y, y.z, y.w};
-    while (msk) {
-      const int k = __builtin_ctz(msk);
-      msk &= msk - 1;
-      const unsigned nv = (xs[k >> 2] >> (8 * (k & 3))) & 0xFFu, ov = (ys[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-      if (pos < cap) seg[pos] = make_uint2(static_cast<unsigned>(r + k), ov | (nv << 8));
-      ++pos;
-    }
-    n += __shfl(pre, 63);
+  }
+  if (cap == 0u) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cl += __shfl_xor(cl, o);
+    n = cl;
   }
   return n;
 }
@@ -582,16 +641,8 @@ __device__ void apply_changes(const KArgs& a, const int32_t* idx, const uint2* l
 // ---- The element-wise passes of the post-sweep phase.  They are functions of their own, not
 // inlined (inlined, they moved the sweep loops' register allocation: spills 85 -> 133 at d = 128),
 // so their pointers say which memory they mean: inside an out-of-line function a plain pointer
-// is generic, and its loads would be flat ones that wait for LDS and global memory alike.
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef double v2d __attribute__((ext_vector_type(2)));
-#define KM_GLOBAL __attribute__((address_space(1)))
-#define KM_LDS __attribute__((address_space(3)))
-template <class T>
-__device__ __forceinline__ T* as_lds(T* p) {
-  return (T*)(KM_LDS T*)p;
-}
+// is generic, and its loads would be flat ones that wait for LDS and global memory alike
+// (KM_GLOBAL, KM_LDS, as_lds: above).
 
 // A thread's slot of the element-wise centre passes: thread (slot tid / 2, half tid % 2) owns
 // the DP / 2 contiguous dims of its half row of Sm as float4s, so the slot's item, problem,
@@ -715,8 +766,6 @@ __device__ __noinline__ void add_sparse_deltas(float* Sm_, St& S_, double* s64_,
     }
   }
 }
-#undef KM_GLOBAL
-#undef KM_LDS
 
 // k-means++ candidate positions for centre S.c[p] (>= 1) of problem p, one wave, from the
 // problem's current closest-distance column (kmeans_shared.hpp).
@@ -1135,10 +1184,16 @@ __device__ __forceinline__ void msum_out(const KArgs& a, State& S, float* Sm, co
   if (hh == 0) S.cnt[msl] = tot;
 }
 
-// Thread 0: admit waiting problems into free seeding slots (followers, ST_FOLLOW, never
+// The scheduler: admit waiting problems into free seeding slots (followers, ST_FOLLOW, never
 // seed), then pack the next sweep: seeding candidates first (they are on every problem's
-// critical path), then Lloyd problems round-robin from S.rr, first fit into the CW slots.
-__device__ void schedule(const KArgs& a, State& S, const int32_t* idx, int dist_cost, bool sparse_ok) {
+// critical path), then Lloyd problems round-robin from S.rr, first fit into the CW slots; then
+// deal the items' E-steps to the waves.
+//
+// schedule() is the serial reference (one thread), compiled only into the diagnostic build
+// -DCC_KM_SCHED_CHECK, where it runs every sweep on a copy of the state and every word of the two
+// states is compared.  schedule_wave() below is the one the engine runs.
+#ifdef CC_KM_SCHED_CHECK
+__device__ __noinline__ void schedule(const KArgs& a, State& S, const int32_t* idx, int dist_cost, bool sparse_ok) {
   const int P = S.P;
   for (int p = 0; p < P && S.seedfree; ++p) {
     if (S.st[p] != ST_WAIT) continue;
@@ -1284,6 +1339,288 @@ __device__ void schedule(const KArgs& a, State& S, const int32_t* idx, int dist_
     S.n_ctiles += static_cast<unsigned long long>((nc + 31) / 32) * a.T;
   }
 }
+#endif  // CC_KM_SCHED_CHECK
+
+// One gathered pass of the tolerance (unit setup): thread (ph, d) = (tid / DP, tid % DP) sums over
+// its rows r = ph, ph + NT / DP, ... of the resample, in increasing r and in f64, the values of
+// dimension d (SQ = false) or their squared deviations from mu (SQ: fma(v, v, q), the contracted
+// form q += v * v compiles to).  KM_TOL_U rows are in flight: all their index loads, then all their
+// row loads, then the additions in row order, so the sum keeps its bits while the pass pays one
+// global round trip per KM_TOL_U rows instead of two dependent ones per row.
+#ifndef KM_TOL_U
+#define KM_TOL_U 16
+#endif
+template <int DP, bool SQ>
+__device__ __noinline__ double tol_pass(const float* X_, const int32_t* idx_, int m, double mu) {
+  const KM_GLOBAL float* X = as_global(X_);
+  const KM_GLOBAL int32_t* idx = as_global(idx_);
+  constexpr int NPH = NT / DP, U = KM_TOL_U;
+  const int d = threadIdx.x % DP, ph = threadIdx.x / DP;
+  const auto add = [&](double s, float x) {
+    if constexpr (SQ) {
+      const double v = static_cast<double>(x) - mu;
+      return __builtin_fma(v, v, s);
+    } else {
+      return s + static_cast<double>(x);
+    }
+  };
+  double s = 0.0;
+  int r = ph;
+  for (; r + (U - 1) * NPH < m; r += U * NPH) {
+    int ix[U];
+    float x[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) ix[u] = idx[r + u * NPH];
+#pragma unroll
+    for (int u = 0; u < U; ++u) x[u] = X[static_cast<size_t>(ix[u]) * DP + d];
+#pragma unroll
+    for (int u = 0; u < U; ++u) s = add(s, x[u]);
+  }
+  for (; r < m; r += NPH) s = add(s, X[static_cast<size_t>(idx[r]) * DP + d]);
+  return s;
+}
+
+// The least loaded wave that still has a free step (strict <: the lowest wave wins a tie).  All
+// operands are wave-uniform and the loops unrolled, so the eight costs and counts live in scalar
+// registers.
+__device__ __forceinline__ int lpt_wave(const int (&wcost)[NW], const int (&nst)[NW], int cap_d, int cap_e) {
+  int w = -1, best = 0;
+#pragma unroll
+  for (int q = 0; q < NW; ++q)
+    if (nst[q] < (q < NDW ? cap_d : cap_e) && (w < 0 || wcost[q] < best)) {
+      w = q;
+      best = wcost[q];
+    }
+  return w;
+}
+
+// The scheduler on wave 0 (all 64 lanes; lane = problem, PMAX = 64): what schedule() computes,
+// field for field.  A lane reads its problem's fields once.  The three sequential walks (admission,
+// the seeding items, the Lloyd items round robin from S.rr, each greedy with skip) run over
+// ballot masks with wave-uniform counters, a problem's few fields fetched by readlane: no LDS
+// round trip per step.  The items, their slots and the per-problem tables are then written by the
+// problems' lanes side by side, and the LPT dealing keeps the eight wave costs and step counts
+// in scalar registers and only stores the steps.  Every capacity and tie rule is schedule()'s.
+// kpp_pos, n_init, m, T: the KArgs fields of those names.
+__device__ void schedule_wave(State& S_, const int32_t* idx_, const int32_t* kpp_pos_, int n_init, int m, int T,
+                              int dist_cost, bool sparse_ok, int lane) {
+  State& S = *as_lds(&S_);
+  const KM_GLOBAL int32_t* idx = as_global(idx_);
+  const KM_GLOBAL int32_t* kpp_pos = as_global(kpp_pos_);
+  const int P = __builtin_amdgcn_readfirstlane(S.P);
+  const bool in = lane < P;
+  int st = in ? S.st[lane] : 0xFF;
+  int c = in ? S.c[lane] : 0;
+  const int K = in ? S.K[lane] : 0, ntr = in ? S.ntr[lane] : 0;
+  const int lead = in ? S.lead[lane] : 0;
+  const int pchg = in ? S.pchg[lane] : 0;
+  // admission: the waiting problems in order take the free seeding slots in order
+  {
+    unsigned seedfree = __builtin_amdgcn_readfirstlane(S.seedfree);
+    unsigned long long wait = __ballot(st == ST_WAIT);
+    int s_new = -1;
+    while (wait && seedfree) {  // wave-uniform
+      const int p = __builtin_ctzll(wait), s = __builtin_ctz(seedfree);
+      wait &= wait - 1;
+      seedfree &= seedfree - 1;
+      if (lane == p) s_new = s;
+    }
+    if (s_new >= 0) {
+      st = ST_SEED;
+      c = 0;
+      S.sslot[lane] = static_cast<unsigned char>(s_new);
+      S.st[lane] = ST_SEED;
+      S.c[lane] = 0;
+    }
+    if (lane == 0) S.seedfree = seedfree;
+  }
+  // seeding items: nt candidates of each seeding problem in order, skipping what does not fit
+  // (an item takes one slot, so the slot count is the item count)
+  int ni = 0, nc = 0, nss2 = 0;
+  int myit = -1;
+  const int ntv = (c == 0) ? 1 : ntr;
+  for (unsigned long long sm = __ballot(st == ST_SEED); sm; sm &= sm - 1) {  // wave-uniform
+    const int p = __builtin_ctzll(sm);
+    const int nt = __builtin_amdgcn_readlane(ntv, p);
+    if (nc + nt > CW || ni + nt > IMAX || nss2 + nt > 2 * (NEW * NSS + NDW * NSS_D)) continue;
+    nss2 += nt;
+    if (lane == p) myit = ni;
+    ni += nt;
+    nc += nt;
+  }
+  const int nis = ni;  // the seeding items are items 0 .. nis - 1, in slots 0 .. nis - 1
+  if (st == ST_SEED && myit >= 0) {
+    const int kind = (c == 0) ? IK_SEED0 : IK_SEED;
+    const int cs = (kind == IK_SEED0) ? 0 : S.cs[lane];
+    const unsigned sslot = S.sslot[lane];
+    for (int t = 0; t < ntv; ++t) {
+      const int it = myit + t;
+      S.ikind[it] = static_cast<unsigned char>(kind);
+      S.iprob[it] = static_cast<unsigned char>(lane);
+      S.ioff[it] = static_cast<short>(it);
+      S.incol[it] = 1;
+      S.itr[it] = static_cast<unsigned char>(t);
+      const int wslot = (kind == IK_SEED0) ? 0 : ((t < cs) ? t : t + 1);
+      S.iw0[it] = (static_cast<unsigned>(kind) << 24) | (static_cast<unsigned>(lane) << 16) | (1u << 8) |
+                  static_cast<unsigned>(it);
+      S.iw1[it] = (static_cast<unsigned>(wslot) << 11) | (static_cast<unsigned>(cs) << 8) |
+                  (static_cast<unsigned>(t) << 5) | sslot;
+      const int pos = (c == 0) ? kpp_pos[S.kidx[lane] * n_init + S.init[lane]] : S.cand[lane][t];
+      S.sitem[it] = static_cast<short>(it);
+      S.scl[it] = -1;
+      S.srow[it] = idx[pos];
+    }
+  }
+  // followers: this sweep gives the leader its centre c; a follower with K = c + 1 then has
+  // all its initial centres and leaves for Lloyd in the post-sweep seeding decision
+  {
+    const int stl = __shfl(st, lead), itl = __shfl(myit, lead), cl = __shfl(c, lead);
+    if (in) S.fgo[lane] = static_cast<unsigned char>(st == ST_FOLLOW && stl == ST_SEED && itl >= 0 && cl + 1 == K);
+  }
+  // Lloyd problems round robin from S.rr: 4-aligned offsets, K padded to a multiple of 4 with
+  // dummy (+inf) slots.  Lane i also keeps the K of the i-th Lloyd item for the dealing below
+  // (at most 44 Lloyd items).
+  const bool lrun = st == ST_RUN || st == ST_FINAL;
+  const int sparse = (sparse_ok && st == ST_RUN && pchg <= m / 8) ? 1 : 0;
+  const int K4 = (K + 3) & ~3;
+  int nls = 0, first_skip = -1, last = -1, nrun = 0, nsp = 0, klloyd = 0;
+  int myoff = 0, itK = 0;
+  const int rr = __builtin_amdgcn_readfirstlane(S.rr);
+  {
+    const unsigned long long rm = __ballot(lrun), below = rr ? (~0ull >> (64 - rr)) : 0ull;
+#pragma unroll 1
+    for (int half = 0; half < 2; ++half)
+      for (unsigned long long q = half ? (rm & below) : (rm & ~below); q; q &= q - 1) {  // wave-uniform
+        const int p = __builtin_ctzll(q);
+        const int Kp = __builtin_amdgcn_readlane(K, p), K4p = __builtin_amdgcn_readlane(K4, p);
+        const int off = (nc + 3) & ~3;
+        if (off + K4p > CW || ni + 1 > IMAX || nls + 1 > NEW * NLS + NDW * NLS_D) {
+          if (first_skip < 0) first_skip = p;
+          continue;
+        }
+        if (lane == p) {
+          myit = ni;
+          myoff = off;
+        }
+        if (lane == nls) itK = Kp;
+        ++ni;
+        ++nls;
+        nc = off + K4p;
+        last = p;
+        klloyd += Kp;
+        nrun += __builtin_amdgcn_readlane(static_cast<int>(st == ST_RUN), p);
+        nsp += __builtin_amdgcn_readlane(sparse, p);
+      }
+  }
+  const bool litem = lrun && myit >= nis;  // (a Lloyd problem's myit was -1 until it was packed)
+  if (litem) {
+    if (myit == nis)
+      for (int s = nis; s < myoff; ++s) {  // alignment gap after the seeding slots
+        S.sitem[s] = -1;
+        S.scl[s] = -1;
+        S.srow[s] = INT_MIN;
+      }
+    const int kind = (st == ST_RUN) ? IK_RUN : IK_FINAL;
+    S.isparse[myit] = static_cast<unsigned char>(sparse);
+    S.ikind[myit] = static_cast<unsigned char>(kind);
+    S.iprob[myit] = static_cast<unsigned char>(lane);
+    S.ioff[myit] = static_cast<short>(myoff);
+    S.incol[myit] = static_cast<short>(K);
+    S.itr[myit] = 0;
+    S.iw0[myit] = (static_cast<unsigned>(1 - S.lcur[lane]) << 30) | (static_cast<unsigned>(kind) << 24) |
+                  (static_cast<unsigned>(lane) << 16) | (static_cast<unsigned>(K) << 8) | static_cast<unsigned>(myoff);
+    S.iw1[myit] = 0;
+    const int cenoff = S.cenoff[lane];
+    const bool msl = st == ST_RUN && !sparse;  // M-step slots
+    for (int s = 0; s < K4; ++s) {
+      S.sitem[myoff + s] = static_cast<short>(s < K ? myit : -1);
+      S.scl[myoff + s] = static_cast<short>((msl && s < K) ? s : -1);
+      S.srow[myoff + s] = (s < K) ? -(cenoff + s) - 1 : INT_MIN;
+    }
+  }
+  if (in) S.pitem[lane] = static_cast<short>(myit);
+  // deal the E-steps to the waves (LPT: heaviest first onto the least loaded wave).  Distance
+  // wave w starts with the cost of its slot tiles' MFMAs (and takes at most NLS_D / NSS_D
+  // steps), E/M wave NDW + q with the M-steps of slot tiles mstep_tile(q) and + NDW (a slot
+  // tile has an M-step when it holds a slot of a dense RUN item)
+  int wcost[NW], nlw[NW], nsw[NW];
+  {
+    const bool dense = litem && st == ST_RUN && !sparse;
+    unsigned mt = 0;  // slot tiles with an M-step
+#pragma unroll
+    for (int j = 0; j < CW / 32; ++j)
+      if (__ballot(dense && (myoff >> 5) <= j && j <= ((myoff + K - 1) >> 5)) != 0ull) mt |= 1u << j;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      wcost[w] = 0;
+      nlw[w] = nsw[w] = 0;
+      if (w < NDW) {
+#pragma unroll
+        for (int j = w; j < CW / 32; j += NDW) wcost[w] += (32 * j < nc) ? dist_cost : 0;
+      } else {
+#pragma unroll
+        for (int j = mstep_tile(w - NDW); j < CW / 32; j += NEW) wcost[w] += ((mt >> j) & 1u) ? KM_COST_MSTEP : 0;
+      }
+    }
+  }
+  static_assert(NW * NLS == 64 && NW * NSS * 2 == 128, "the step tables are reset a lane each");
+  (&S.lstep[0][0])[lane] = 0xFF;
+  (&S.sstep[0][0][0])[2 * lane] = 0xFF;
+  (&S.sstep[0][0][0])[2 * lane + 1] = 0xFF;
+  for (int i = 0; i < nls; ++i) {  // Lloyd items were appended after the seeding items; wave-uniform
+    const int Ki = __builtin_amdgcn_readlane(itK, i);
+    const int w = lpt_wave(wcost, nlw, NLS_D, NLS);
+    int n = 0;
+#pragma unroll
+    for (int q = 0; q < NW; ++q)
+      if (q == w) {
+        n = nlw[q]++;
+        wcost[q] += (Ki + 7) / 8 * KM_COST_LCHUNK + KM_COST_LBASE;
+      }
+    if (lane == 0) S.lstep[w][n] = static_cast<unsigned char>(nis + i);
+  }
+  for (int it = 0; it < nis; it += 2) {  // a seeding step takes two items, one per half-wave
+    const int w = lpt_wave(wcost, nsw, NSS_D, NSS);
+    int n = 0;
+#pragma unroll
+    for (int q = 0; q < NW; ++q)
+      if (q == w) {
+        n = nsw[q]++;
+        wcost[q] += KM_COST_SSTEP;
+      }
+    if (lane == 0) {
+      S.sstep[w][n][0] = static_cast<unsigned char>(it);
+      if (it + 1 < nis) S.sstep[w][n][1] = static_cast<unsigned char>(it + 1);
+    }
+  }
+  {
+    int ln = 0, sn = 0;
+#pragma unroll
+    for (int q = 0; q < NW; ++q) {
+      ln = (lane == q) ? nlw[q] : ln;
+      sn = (lane == q) ? nsw[q] : sn;
+    }
+    if (lane < NW) {
+      S.nlw[lane] = static_cast<unsigned char>(ln);
+      S.nsw[lane] = static_cast<unsigned char>(sn);
+    }
+  }
+  if (lane == 0) {
+    S.rr = (first_skip >= 0) ? first_skip : (last >= 0 ? (last + 1) % P : rr);
+    S.nitems = ni;
+    S.ncols = nc;
+    S.n_seed += static_cast<unsigned long long>(nis) * m;
+    S.n_lloyd += static_cast<unsigned long long>(klloyd) * m;
+    S.n_mrows += static_cast<unsigned long long>(nrun) * m;
+    S.n_sparse += static_cast<unsigned>(nsp);
+    if (ni > 0) {
+      S.n_sweeps += 1;
+      S.n_ctiles += static_cast<unsigned long long>((nc + 31) / 32) * T;
+    }
+  }
+}
+#undef KM_GLOBAL
+#undef KM_LDS
 
 template <int DP>
 __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
@@ -1322,6 +1659,7 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
     const int h = a.h_begin + hb;
     const int32_t* idx = a.idx + static_cast<size_t>(h) * m;
     const int32_t* gd = a.units + g * US;
+    KM_STAMP(us0);
 
     // ---- problem table --------------------------------------------------------
     if (tid == 0) {
@@ -1360,7 +1698,9 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
     }
     __syncthreads();
     const int P = S.P;
+    KM_STAMP(us1);
     for (size_t e = tid; e < static_cast<size_t>(2 * P) * a.lsm; e += NT) glab[e] = 0xFF;  // 2 buffers per problem
+    KM_STAMP(us2);
 
     // ---- tol = tol_rel * mean(var(X_sub, axis=0)) (sklearn _tolerance, :270-278) --
     {
@@ -1368,9 +1708,7 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
       double* mean = reinterpret_cast<double*>(ring) + NT;
       constexpr int NPH = NT / DP;
       const int d = tid % DP, ph = tid / DP;
-      double s = 0.0;
-      for (int r = ph; r < m; r += NPH) s += static_cast<double>(a.X[static_cast<size_t>(idx[r]) * DP + d]);
-      red[ph * DP + d] = s;
+      red[ph * DP + d] = tol_pass<DP, false>(a.X, idx, m, 0.0);
       __syncthreads();
       if (tid < DP) {
         double t = 0.0;
@@ -1378,12 +1716,7 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
         mean[tid] = t / m;
       }
       __syncthreads();
-      const double mu = mean[d];
-      double q = 0.0;
-      for (int r = ph; r < m; r += NPH) {
-        const double v = static_cast<double>(a.X[static_cast<size_t>(idx[r]) * DP + d]) - mu;
-        q += v * v;
-      }
+      const double q = tol_pass<DP, true>(a.X, idx, m, mean[d]);
       __syncthreads();
       red[ph * DP + d] = q;
       __syncthreads();
@@ -1398,20 +1731,48 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
       }
       __syncthreads();
     }
+    KM_STAMP(us3);
 
     // ---- sweeps -----------------------------------------------------------------
     for (;;) {
       KM_STAMP(swp);
-      if (tid == 0) {
-        // d <= 64 (pair mode): the larger kernel body would leave these helpers out of line and
-        // the KArgs copied to scratch; inline them there (at d = 128 the default choice stands)
+#ifdef CC_KM_SCHED_CHECK
+      // the state before scheduling, copied for the serial reference (the barrier at the end of
+      // the last sweep, or of the unit setup, has made it final)
+      for (unsigned e = tid; e < sizeof(State) / 4; e += NT)
+        reinterpret_cast<unsigned*>(wsb + a.off_chk)[e] = reinterpret_cast<const unsigned*>(&S)[e];
+      __syncthreads();
+#endif
+      if (wave == 0) {
+        // out of line at every width, so that it cannot move the sweep loops' register allocation
+        // (it takes no KArgs, so none is copied to scratch for it; KM_SCHED_INLINE: the inlined
+        // form at d <= 64, where the serial scheduler was inlined: VGPR spills 23 / 44 against 10 / 39)
+#ifdef KM_SCHED_INLINE
         if constexpr (kPair<DP>) {
-          [[clang::always_inline]] schedule(a, S, idx, dist_cost<DP>(), kSparse<DP> && !cc_km_dense_only);
-        } else {
-          schedule(a, S, idx, dist_cost<DP>(), kSparse<DP> && !cc_km_dense_only);
+          [[clang::always_inline]] schedule_wave(S, idx, a.kpp_pos, a.n_init, m, T, dist_cost<DP>(),
+                                                 kSparse<DP> && !cc_km_dense_only, lane);
+        } else
+#endif
+        {
+          [[clang::noinline]] schedule_wave(S, idx, a.kpp_pos, a.n_init, m, T, dist_cost<DP>(),
+                                            kSparse<DP> && !cc_km_dense_only, lane);
         }
       }
+      KM_STAMP(sch1);
       __syncthreads();
+#ifdef CC_KM_SCHED_CHECK
+      {
+        State& R = *reinterpret_cast<State*>(wsb + a.off_chk);
+        if (tid == 0) schedule(a, R, idx, dist_cost<DP>(), kSparse<DP> && !cc_km_dense_only);
+        __syncthreads();
+        unsigned bad = 0;
+        for (unsigned e = tid; e < sizeof(State) / 4; e += NT)
+          bad += reinterpret_cast<const unsigned*>(&R)[e] != reinterpret_cast<const unsigned*>(&S)[e];
+        if (bad && a.stats) atomicAdd(&a.stats[122], static_cast<unsigned long long>(bad));
+        if (tid == 0 && a.stats && S.nitems > 0) atomicAdd(&a.stats[123], 1ull);  // as n_sweeps counts
+        __syncthreads();
+      }
+#endif
       const int nitems = S.nitems, ncols = S.ncols;
       if (nitems == 0) break;
 
@@ -1715,22 +2076,20 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
           cpos[p * a.Kws + c] = (c == 0) ? a.kpp_pos[S.kidx[p] * a.n_init + S.init[p]] : S.cand[p][k.best];
           S.c[p] = static_cast<unsigned char>(c + 1);
           if (c + 1 == S.K[p]) {
-            S.to_run[p] = 1;  // seeding slot released below (single writer)
+            S.to_run[p] = 1;
           } else {
             S.need_sel[p] = 1;
           }
         }
+        if (S.to_run[p]) {  // to Lloyd; the problem's thread releases its seeding slot
+          if (S.st[p] == ST_SEED)  // a follower holds none
+            __hip_atomic_fetch_or(&S.seedfree, 1u << S.sslot[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          S.st[p] = ST_RUN;
+          S.iter[p] = 0;
+          S.pchg[p] = a.m;
+        }
       }
       __syncthreads();
-      if (tid == 0) {
-        for (int p = 0; p < P; ++p)
-          if (S.to_run[p]) {
-            if (S.st[p] == ST_SEED) S.seedfree |= 1u << S.sslot[p];  // a follower holds none
-            S.st[p] = ST_RUN;
-            S.iter[p] = 0;
-            S.pchg[p] = a.m;
-          }
-      }
       // candidate selection: one wave per problem
       {
         int j = 0;
@@ -1803,12 +2162,15 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
         }
       }
       __syncthreads();
-      if (tid == 0)
-        for (int it = 0; it < nitems; ++it)
-          if (S.ikind[it] >= IK_RUN) {
-            S.lcur[S.iprob[it]] = static_cast<unsigned char>(1 - S.lcur[S.iprob[it]]);
-            if (S.ikind[it] == IK_RUN) S.n_changes += static_cast<unsigned>(S.pchg[S.iprob[it]]);
-          }
+      KM_STAMP(fl0);
+      if (tid == 0) S.flag = 0;  // "a RUN item has an empty cluster", set in the M-step completion
+      if (tid < nitems && S.ikind[tid] >= IK_RUN) {  // thread per item (a problem has one item)
+        const int p = S.iprob[tid];
+        S.lcur[p] = static_cast<unsigned char>(1 - S.lcur[p]);
+        if (S.ikind[tid] == IK_RUN)
+          __hip_atomic_fetch_add(&S.n_changes, static_cast<unsigned long long>(static_cast<unsigned>(S.pchg[p])),
+                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
       __syncthreads();
       KM_STAMP(ppB);
 
@@ -1853,19 +2215,15 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
 
       KM_STAMP(ppC);
       // ---- Lloyd M-step completion (RUN items) ------------------------------------
-      if (tid == 0) {
-        int f = 0;
-        for (int it = 0; it < nitems; ++it) {
-          if (S.ikind[it] != IK_RUN) continue;
-          const int p = S.iprob[it], off = S.ioff[it];
-          int ne = 0;
-          for (int c = 0; c < S.K[p]; ++c) ne += (S.cnt[off + c] == 0);
-          S.nempty[p] = ne;
-          f |= (ne > 0);
-        }
-        S.flag = f;
+      if (tid < nitems && S.ikind[tid] == IK_RUN) {  // thread per item (S.flag: 0 since the flip above)
+        const int p = S.iprob[tid], off = S.ioff[tid];
+        int ne = 0;
+        for (int c = 0; c < S.K[p]; ++c) ne += (S.cnt[off + c] == 0);
+        S.nempty[p] = ne;
+        if (ne > 0) S.flag = 1;
       }
       __syncthreads();
+      KM_STAMP(ec1);
       if (S.flag) {
         for (int it = 0; it < nitems; ++it) {
           if (S.ikind[it] != IK_RUN) continue;
@@ -1948,6 +2306,8 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
         atomicAdd(&a.stats[108], ppC - ppB);
         atomicAdd(&a.stats[109], pp1 - ppC);
         atomicAdd(&a.stats[116], cu1 - cu0);  // of the centre update: the shift pass
+        atomicAdd(&a.stats[118], sch1 - swp);  // of the sweep prologue: the scheduler
+        atomicAdd(&a.stats[121], (ec1 - ppC) + (ppB - fl0));  // empty-cluster count, label-buffer flip
       }
       // sweep cycles and counts by width (active 32-slot waves 1..8), all workgroups
       if (tid == 0 && a.stats) {
@@ -1963,12 +2323,22 @@ __global__ __launch_bounds__(NT, 1) void kmeans_kernel(KArgs a) {
     }
 
     // ---- best of n_init per K, output (KMeans.fit :1495-1531) -------------------
+    KM_STAMP(out0);
     for (int p0 = 0; p0 < P; p0 += a.n_init) {
       const auto lab = [&](int p) { return glab + static_cast<size_t>(2 * p + S.lcur[p]) * a.lsm; };
       const int best = best_of_inits<NT, KMAX>(p0, a.n_init, m, lab, [&](int p) { return S.inert[p]; }, S.map, S.flag, tid);
       write_fit<NT>(lab(best), idx, m, a.labels_out, a.n, a.ldl, S.kidx[p0], h, a.H, S.inert[best], S.iter[best],
                     a.inertia_out, a.niter_out, tid);
     }
+#ifdef CC_KM_STAMPS
+    KM_STAMP(out1);
+    if (blockIdx.x == 0 && tid == 0 && a.stats) {  // unit setup (of it: tol passes, label fill), output
+      atomicAdd(&a.stats[74], us3 - us0);
+      atomicAdd(&a.stats[119], us3 - us2);
+      atomicAdd(&a.stats[120], us2 - us1);
+      atomicAdd(&a.stats[75], out1 - out0);
+    }
+#endif
   }
   if (tid == 0 && a.stats) {
     atomicAdd(&a.stats[0], S.n_lloyd);
@@ -1998,7 +2368,7 @@ __global__ void split_kernel(const float* X, long long total, int dpad, float sc
 struct WsLayout {
   int Pws = 0, Cws = 0, Kws = 0, Tws = 0, lseg = 0;
   size_t off_cen = 0, off_cenn = 0, off_cpos = 0, off_dbuf = 0, off_rdist = 0, off_s64 = 0, off_c64 = 0,
-         off_list = 0, per_wg = 0;
+         off_list = 0, off_chk = 0, per_wg = 0;
 };
 
 // Change-list entries per problem and wave segment (a segment covers m / 8 rows): a sparse
@@ -2033,7 +2403,11 @@ WsLayout ws_layout(int m, int dpad, const int32_t* units, int nU, int seedmax) {
   L.off_c64 = L.off_s64 + (sp ? al(static_cast<size_t>(L.Cws) * dpad * sizeof(double)) : 0);
   L.off_list = L.off_c64 + (sp ? al(static_cast<size_t>(L.Cws) * sizeof(int)) : 0);
   L.lseg = list_seg(m);
-  L.per_wg = L.off_list + (sp ? al(static_cast<size_t>(L.Pws) * NW * L.lseg * sizeof(uint2)) : 0);
+  L.off_chk = L.off_list + (sp ? al(static_cast<size_t>(L.Pws) * NW * L.lseg * sizeof(uint2)) : 0);
+  L.per_wg = L.off_chk;
+#ifdef CC_KM_SCHED_CHECK
+  L.per_wg += al(sizeof(State));
+#endif
   return L;
 }
 
@@ -2224,6 +2598,9 @@ extern "C" int cc_kmeans_batched(const float* X, const uint16_t* Xhl, const floa
   a.off_c64 = L.off_c64;
   a.off_list = L.off_list;
   a.lseg = L.lseg;
+#ifdef CC_KM_SCHED_CHECK
+  a.off_chk = L.off_chk;
+#endif
   a.Pws = L.Pws;
   a.Kws = L.Kws;
   a.Tws = L.Tws;

@@ -29,7 +29,12 @@ for w in range(8):
     v = st[8 + 8 * w: 15 + 8 * w]
     tot = max(v.sum(), 1)
     print(f"wave {w}:", {n: f"{x / 1e6:.1f}M ({100 * x / tot:.0f}%)" for n, x in zip(names, v)})
-print("post-processing cycles (wg0):", st[73] / 1e6, "M")
+print("sweep prologue of wave 0 (wg0, Mcycles): %.1f, of it the scheduler %.1f, the rest %.1f"
+      % (st[14] / 1e6, st[118] / 1e6, (st[14] - st[118]) / 1e6))
+print("unit setup (wg0, Mcycles): %.1f, of it the tol passes %.1f, the label fill %.1f; output %.1f"
+      % (st[74] / 1e6, st[119] / 1e6, st[120] / 1e6, st[75] / 1e6))
+print("post-processing cycles (wg0):", st[73] / 1e6, "M; of them the per-problem / per-item sections "
+      "(slot release, empty-cluster count, label-buffer flip) %.2f M" % (st[121] / 1e6))
 it = cc.kmeans_n_iter_.cpu().numpy()
 print("n_iter per K (mean/max over h):", {K: (round(float(it[k].mean()), 1), int(it[k].max()))
                                           for k, K in enumerate(cfg["Ks"])})
