@@ -76,6 +76,10 @@ SIGNATURES = {
     "cc_kpp_tables": (_c_int, [_vp, _c_int, _c_int, _c_u32, _c_int, _c_int, _vp, _c_int, _vp]),
     "cc_prepare_rows_scratch_bytes": (_c_sz, [_c_int, _c_int]),
     "cc_prepare_rows": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "cc_kmeans_dpad": (_c_int, [_c_int]),
+    "cc_scale_exponent": (_c_int, [ctypes.c_float, _vp]),
+    "cc_kmeans_launch_plan": (_c_int, [_c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_sz,
+                                       _c_sz, _c_int, _c_int, _c_int, _vp, _c_int]),
     "cc_kmeans_fit_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int, _c_int, _vp, _c_int, _c_int,
                                               _c_int]),
     "cc_kmeans_fit": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int,

@@ -23,7 +23,6 @@ import torch
 from . import _lib, engine
 
 USTRIDE = 1 + 4 * 64   # CC_KM_USTRIDE
-DPADS = (32, 64, 128)
 
 
 _WORKSPACE = {}
@@ -47,17 +46,6 @@ def release_workspace():
     _WORKSPACE.clear()
 
 
-def dpad_for(d: int) -> int:
-    """Feature padding: 32/64/128 for the on-chip engine (cc_kmeans_batched), a multiple of 32
-    for the wide-row path (cc_kmeans_wide, d > 128)."""
-    if d <= 0:
-        raise ValueError("X must have at least one feature")
-    for p in DPADS:
-        if d <= p:
-            return p
-    return (d + 31) // 32 * 32
-
-
 def local_trials(K: int) -> int:
     return 2 + int(np.log(K))
 
@@ -72,32 +60,6 @@ def plan(Ks, n_init: int, n_sub: int = 1) -> np.ndarray:
     if nU <= 0:
         _lib.check(nU, "cc_kmeans_plan")
     return buf[:nU].copy()
-
-
-def choose_subsets(nh: int, n_groups: int, cus: int) -> int:
-    """Units per resample: enough units to fill every CU of the persistent grid with a
-    balanced last round, as few as possible (bigger units pack their sweeps better)."""
-    best, best_eff = 1, -1.0
-    for s in range(1, max(1, n_groups) + 1):
-        units = nh * s
-        rounds = -(-units // cus)
-        eff = units / (cus * rounds) if units >= cus else units / cus
-        if eff >= 0.85:
-            return s
-        if eff > best_eff + 1e-9:
-            best, best_eff = s, eff
-    return best
-
-
-def default_seedmax(m: int) -> int:
-    """Problems of a unit that may seed (k-means++) concurrently.  Each seeding problem keeps
-    closest-distance columns of m rows in the workspace (7 x m f32 per slot), so the cap shrinks
-    with m (<= ~110 MB of columns per workgroup).  Measured (k-means launch, round 3, with the
-    workspace budget not binding): C3 m = 40k: 12 / 16 / 20 / 24 / 32 -> 1679 / 1670 / 1656 /
-    1645 / 1647 ms; C5 m = 160k: 6 / 8 / 12 / 16 / 20 / 24 / 32 -> 281 / 283 / 276 / 276 / 275 /
-    273 / 273 ms; C2 m = 8k: 12 / 20 / 32 -> 88.2 / 87.5 / 87.0 ms.  (Round 1 measured 6 best
-    at C5: there the larger caps passed the 8 GB budget and halved the grid.)"""
-    return max(2, min(24, 4_000_000 // max(int(m), 1)))
 
 
 def kpp_tables(Ks, n_init: int, seed: int, m: int, weight_dtype=np.float32):
@@ -116,15 +78,6 @@ def kpp_tables(Ks, n_init: int, seed: int, m: int, weight_dtype=np.float32):
     return u, pos, stride
 
 
-def scale_exponent(amax: float) -> int:
-    """e with max|X| * 2^e <= 2^14, so the f16 hi/lo operand pair stays in range."""
-    if not np.isfinite(amax):
-        raise ValueError("X contains non-finite values")
-    if amax == 0.0:
-        return 0
-    return int(np.clip(14 - int(np.ceil(np.log2(amax))), -62, 62))
-
-
 def prepare_rows(X, device):
     """Mean-centred float32 rows zero-padded to dpad, their squared norms, and the f16 hi/lo
     MFMA operand image of the rows, on device (native cc_prepare_rows, the same preparation
@@ -135,13 +88,15 @@ def prepare_rows(X, device):
     so one global centring serves every resample.  Returns (Xd, xnorm, dpad, Xhl, e).
     """
     n, d = X.shape
-    dpad = dpad_for(d)
+    if d <= 0:
+        raise ValueError("X must have at least one feature")
+    lib = _lib.load()
+    dpad = lib.cc_kmeans_dpad(int(d))
     Xt = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X))
     Xt = Xt.to(device=device, dtype=torch.float32).contiguous()
     Xd = torch.empty((n, dpad), dtype=torch.float32, device=device)
     xnorm = torch.empty((n,), dtype=torch.float32, device=device)
     Xhl = torch.empty((n, 2, dpad), dtype=torch.int16, device=device)
-    lib = _lib.load()
     scratch = torch.empty(int(lib.cc_prepare_rows_scratch_bytes(n, d)), dtype=torch.uint8, device=device)
     e = ctypes.c_int(0)
     _lib.call("cc_prepare_rows", Xt.data_ptr(), n, d, dpad, Xd.data_ptr(), xnorm.data_ptr(),
@@ -151,6 +106,29 @@ def prepare_rows(X, device):
 
 
 DEFAULT_WORKSPACE_BUDGET = 40 << 30
+ENGINES = ("cc_kmeans_batched", "cc_kmeans_wide", "cc_kmeans_f64")  # CC_KM_ENGINE_*
+UNLIMITED = (1 << 64) - 1
+
+
+class _Call(ctypes.Structure):  # cc_km_call
+    _fields_ = [(f, ctypes.c_int32) for f in ("engine", "k0", "nk", "par", "n_sub", "seedmax")] + \
+               [("ws_bytes", ctypes.c_uint64)]
+
+
+def launch_plan(d, m, nh, Ks, n_init, precision, cus, budget, budget_hard, n_sub=0, seedmax=0, grid=0):
+    """The engine calls of a fit, in order (native cc_kmeans_launch_plan, the planner cc_kmeans_fit
+    follows too; no device needed).  One dict per call: engine (the entry point's name), k0 and nk
+    (the call fits Ks[k0:k0 + nk]), par (workgroups; resamples per batch for cc_kmeans_wide), n_sub
+    and seedmax (cc_kmeans_batched only) and ws_bytes, the engine workspace of the call."""
+    Ks_np = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
+    buf = (_Call * max(len(Ks_np), 1))()
+    nc = _lib.load().cc_kmeans_launch_plan(int(d), int(m), int(nh), Ks_np.ctypes.data, len(Ks_np), int(n_init),
+                                           int(precision), int(cus), int(budget), int(budget_hard), int(n_sub),
+                                           int(seedmax), int(grid), ctypes.addressof(buf), len(buf))
+    if nc <= 0:
+        _lib.check(nc or -1, "cc_kmeans_launch_plan")
+    return [dict(engine=ENGINES[c.engine], k0=c.k0, nk=c.nk, par=c.par, n_sub=c.n_sub, seedmax=c.seedmax,
+                 ws_bytes=c.ws_bytes) for c in buf[:nc]]
 
 
 class BatchedKMeans:
@@ -171,6 +149,32 @@ class BatchedKMeans:
         self.stats = None
         self.units = None
         self.wide_calls = None
+        self.calls = None  # the launch_plan of the last run
+
+    def _launch(self, dev, d, m, nh, precision, budget, budget_hard, weight_dtype, outputs, launch, grid=0):
+        """Plan the fit for this device and the two byte budgets (CCMI_NSUB / CCMI_SEEDMAX override the
+        units per resample / concurrent seeders) and make each call: launch(call, Ks, fit, ws) with
+        its K values, the arguments every engine takes from n_init to n_iter, the cached workspace."""
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        self.calls = launch_plan(d, m, nh, self.Ks, self.n_init, precision, cus, budget, budget_hard,
+                                 n_sub=int(os.environ.get("CCMI_NSUB", 0)),
+                                 seedmax=int(os.environ.get("CCMI_SEEDMAX", 0)) or self.seedmax or 0,
+                                 grid=grid or 0)
+        labels_nh, inertia, n_iter = outputs
+        for c in self.calls:
+            k0 = c["k0"]
+            Ks = np.ascontiguousarray(np.asarray(self.Ks[k0:k0 + c["nk"]], dtype=np.int32))
+            u, pos, stride = kpp_tables(Ks, self.n_init, self.seed, m, weight_dtype)
+            u_d = torch.from_numpy(u).to(dev)
+            pos_d = torch.from_numpy(pos).to(dev)
+            ws = workspace(dev, c["ws_bytes"])
+            fit = (self.n_init, self.max_iter, self.tol, u_d.data_ptr(), stride, pos_d.data_ptr(),
+                   labels_nh[k0].data_ptr(), labels_nh.stride(1),
+                   None if inertia is None else inertia[k0].data_ptr(),
+                   None if n_iter is None else n_iter[k0].data_ptr())
+            with engine.timed(c["engine"]):
+                launch(c, Ks, fit, (ws.data_ptr(), ws.numel()))
+        return labels_nh
 
     def run(self, Xd, xnorm, dreal, idx_d, n, H, m, h_begin, h_end, labels_nh, weight_dtype,
             inertia=None, n_iter=None, Xhl=None, scale_exp=None):
@@ -184,37 +188,35 @@ class BatchedKMeans:
         self.stats = torch.zeros(128, dtype=torch.int64, device=dev)  # [0:8] counters, rest: diagnostics
         if nh <= 0:
             return labels_nh
-        if Xd.shape[1] > DPADS[-1]:
-            return self._run_wide(Xd, xnorm, dreal, idx_d, n, H, m, h_begin, h_end, labels_nh,
-                                  weight_dtype, inertia, n_iter, Xhl, scale_exp)
-        cus = torch.cuda.get_device_properties(dev).multi_processor_count
-        n_sub = int(os.environ.get("CCMI_NSUB", 0)) or choose_subsets(nh, len(self.Ks), cus)
-        u_h = plan(self.Ks, self.n_init, n_sub)
-        self.units = u_h
-        nU = u_h.shape[0]
-        seedmax = max(1, min(int(os.environ.get("CCMI_SEEDMAX", 0)) or self.seedmax or default_seedmax(m),
-                             32, int(u_h[:, 0].max())))
-        u, pos, stride = kpp_tables(self.Ks, self.n_init, self.seed, m, weight_dtype)
-        u_d = torch.from_numpy(u).to(dev)
-        pos_d = torch.from_numpy(pos).to(dev)
-        u_d_units = torch.from_numpy(u_h).to(dev)
-        lib = _lib.load()
-        per = lambda g: lib.cc_kmeans_workspace_bytes(m, Xd.shape[1], u_h.ctypes.data, nU, seedmax, g)
-        grid = min(cus, nh * nU)
-        budget = min(self.workspace_budget or DEFAULT_WORKSPACE_BUDGET, int(0.5 * torch.cuda.mem_get_info(dev)[0]))
-        while grid > 1 and per(grid) > budget:
-            grid //= 2
-        ws = workspace(dev, per(grid))
-        ldl = labels_nh.stride(1)
-        with engine.timed("cc_kmeans_batched"):
-            _lib.call("cc_kmeans_batched", Xd.data_ptr(), Xhl.data_ptr(), xnorm.data_ptr(), n,
-                      int(dreal), Xd.shape[1], int(scale_exp), idx_d.data_ptr(), H, m, h_begin,
-                      h_end, u_d_units.data_ptr(), u_h.ctypes.data, nU, self.n_init,
-                      self.max_iter, self.tol, u_d.data_ptr(), stride, pos_d.data_ptr(),
-                      labels_nh.data_ptr(), ldl, _lib.ptr(inertia), _lib.ptr(n_iter),
-                      self.stats.data_ptr(), ws.data_ptr(), ws.numel(), grid, seedmax,
-                      engine.stream_ptr(dev))
-        return labels_nh
+        dpad = Xd.shape[1]
+        rows = (Xd.data_ptr(), Xhl.data_ptr(), xnorm.data_ptr(), n, int(dreal), dpad, int(scale_exp),
+                idx_d.data_ptr(), H, m, h_begin, h_end)
+        if dpad > 128:  # cc_kmeans_batched takes dpad 32 / 64 / 128 only
+            return self._run_wide(dev, rows, dpad, m, nh, weight_dtype, (labels_nh, inertia, n_iter))
+
+        def batched(c, Ks, fit, ws):
+            self.units = u_h = plan(self.Ks, self.n_init, c["n_sub"])
+            u_d_units = torch.from_numpy(u_h).to(dev)
+            _lib.call("cc_kmeans_batched", *rows, u_d_units.data_ptr(), u_h.ctypes.data, u_h.shape[0], *fit,
+                      self.stats.data_ptr(), *ws, c["par"], c["seedmax"], engine.stream_ptr(dev))
+
+        return self._launch(dev, dpad, m, nh, 0, self.workspace_budget or DEFAULT_WORKSPACE_BUDGET,
+                            int(0.5 * torch.cuda.mem_get_info(dev)[0]), weight_dtype,
+                            (labels_nh, inertia, n_iter), batched)
+
+    def _run_wide(self, dev, rows, dpad, m, nh, weight_dtype, outputs):
+        """d > 128: cc_kmeans_wide over batches of resamples sized to the workspace budget, one
+        call per list of K values that cc_kmeans_wide_chunk deals (the planner asks it; a K that
+        fits no call alone raises there, naming K and n_init)."""
+        self.wide_calls = []  # the K values of each cc_kmeans_wide call
+
+        def wide(c, Ks, fit, ws):
+            self.wide_calls.append(Ks.tolist())
+            _lib.call("cc_kmeans_wide", *rows, Ks.ctypes.data, len(Ks), *fit, self.stats.data_ptr(), *ws,
+                      c["par"], engine.stream_ptr(dev))
+
+        return self._launch(dev, dpad, m, nh, 0, self.wide_budget,
+                            int(0.6 * torch.cuda.mem_get_info(dev)[0]), weight_dtype, outputs, wide)
 
     def run_f64(self, X64, idx_d, n, H, m, h_begin, h_end, labels_nh, inertia=None, n_iter=None,
                 grid=None):
@@ -226,90 +228,18 @@ class BatchedKMeans:
         nh = h_end - h_begin
         if nh <= 0:
             return labels_nh
-        lib = _lib.load()
         d = X64.shape[1]
-        cus = torch.cuda.get_device_properties(dev).multi_processor_count
-        for k0 in range(0, len(self.Ks), 64):  # cc_kmeans_f64 takes <= 64 K values per call
-            Ks = self.Ks[k0:k0 + 64]
-            Ks_np = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
-            g = int(grid or min(4 * cus, nh * len(Ks)))
-            per = lambda gg: lib.cc_kmeans_f64_workspace_bytes(m, d, Ks_np.ctypes.data, len(Ks), gg, nh)
-            # never more than half the free device memory.  At the DEFAULT budget the grid keeps two
-            # resident workgroups per CU (the kernel's occupancy) even when their scratch exceeds
-            # the budget: with one per CU the float64 fit runs ~1.25x longer
-            # (profiles/r04/f64_budget_r4ak.txt).  A budget the caller set is never exceeded.
-            free_half = int(0.5 * torch.cuda.mem_get_info(dev)[0])
-            if self.workspace_budget is None:
-                cap = min(max(DEFAULT_WORKSPACE_BUDGET, per(min(g, 2 * cus))), free_half)
-            else:
-                cap = min(self.workspace_budget, free_half)
-            if per(g) > cap:  # the largest grid that fits (per(g) is non-decreasing in g)
-                lo, hi = 1, g
-                while lo < hi:
-                    mid = (lo + hi + 1) // 2
-                    if per(mid) <= cap:
-                        lo = mid
-                    else:
-                        hi = mid - 1
-                g = lo
-            ws = workspace(dev, per(g))
-            u, pos, stride = kpp_tables(Ks, self.n_init, self.seed, m, np.float64)
-            u_d = torch.from_numpy(u).to(dev)
-            pos_d = torch.from_numpy(pos).to(dev)
-            with engine.timed("cc_kmeans_f64"):
-                _lib.call("cc_kmeans_f64", X64.data_ptr(), n, d, idx_d.data_ptr(), H, m, h_begin,
-                          h_end, Ks_np.ctypes.data, len(Ks), self.n_init, self.max_iter, self.tol,
-                          u_d.data_ptr(), stride, pos_d.data_ptr(), labels_nh[k0].data_ptr(),
-                          labels_nh.stride(1),
-                          None if inertia is None else inertia[k0].data_ptr(),
-                          None if n_iter is None else n_iter[k0].data_ptr(), ws.data_ptr(),
-                          ws.numel(), g, engine.stream_ptr(dev))
-        return labels_nh
 
-    def _run_wide(self, Xd, xnorm, dreal, idx_d, n, H, m, h_begin, h_end, labels_nh, weight_dtype,
-                  inertia, n_iter, Xhl, scale_exp):
-        """d > 128: cc_kmeans_wide over batches of resamples sized to the workspace budget.  Each
-        call takes the next K values in K_range order that fit it (cc_kmeans_wide_chunk: at most
-        64 (K, init) problems within the engine's centroid capacity, the rule cc_kmeans_fit
-        follows too); a K that fits no call alone raises, naming K and n_init."""
-        dev = Xd.device
-        lib = _lib.load()
-        dpad = Xd.shape[1]
-        nh = h_end - h_begin
-        free = torch.cuda.mem_get_info(dev)[0]
-        budget = min(self.wide_budget, int(0.6 * free))
-        ldl = labels_nh.stride(1)
-        all_Ks = np.ascontiguousarray(np.asarray(self.Ks, dtype=np.int32))
-        self.wide_calls = []  # the K values of each cc_kmeans_wide call
-        k0 = per_call = 0
-        while k0 + per_call < len(self.Ks):
-            k0 += per_call
-            per_call = lib.cc_kmeans_wide_chunk(m, dpad, all_Ks[k0:].ctypes.data, len(self.Ks) - k0, self.n_init)
-            if per_call <= 0:
-                _lib.check(per_call or -1, "cc_kmeans_wide_chunk")
-            Ks = self.Ks[k0:k0 + per_call]
-            self.wide_calls.append(Ks)
-            Ks_np = np.ascontiguousarray(all_Ks[k0:k0 + per_call])
-            ws1 = lib.cc_kmeans_wide_workspace_bytes(m, dpad, Ks_np.ctypes.data, len(Ks),
-                                                     self.n_init, 1)
-            ws2 = lib.cc_kmeans_wide_workspace_bytes(m, dpad, Ks_np.ctypes.data, len(Ks),
-                                                     self.n_init, 2)
-            if ws1 == 0:
-                _lib.check(-1, "cc_kmeans_wide_workspace_bytes")
-            per = ws2 - ws1
-            cap = int(max(1, min(nh, (budget - (ws1 - per)) // per)))
-            batch = -(-nh // -(-nh // cap))  # equal batches: one round-count tail per batch
-            ws = workspace(dev, ws1 + per * (batch - 1))
-            u, pos, stride = kpp_tables(Ks, self.n_init, self.seed, m, weight_dtype)
-            u_d = torch.from_numpy(u).to(dev)
-            pos_d = torch.from_numpy(pos).to(dev)
-            with engine.timed("cc_kmeans_wide"):
-                _lib.call("cc_kmeans_wide", Xd.data_ptr(), Xhl.data_ptr(), xnorm.data_ptr(), n,
-                          int(dreal), dpad, int(scale_exp), idx_d.data_ptr(), H, m, h_begin, h_end,
-                          Ks_np.ctypes.data, len(Ks), self.n_init, self.max_iter, self.tol,
-                          u_d.data_ptr(), stride, pos_d.data_ptr(), labels_nh[k0].data_ptr(), ldl,
-                          None if inertia is None else inertia[k0].data_ptr(),
-                          None if n_iter is None else n_iter[k0].data_ptr(),
-                          self.stats.data_ptr(), ws.data_ptr(), ws.numel(), batch,
-                          engine.stream_ptr(dev))
-        return labels_nh
+        def f64(c, Ks, fit, ws):
+            _lib.call("cc_kmeans_f64", X64.data_ptr(), n, d, idx_d.data_ptr(), H, m, h_begin, h_end,
+                      Ks.ctypes.data, len(Ks), *fit, *ws, c["par"], engine.stream_ptr(dev))
+
+        # never more than half the free device memory; the planner may exceed the DEFAULT budget up
+        # to that to keep the kernel's occupancy, never a budget the caller set
+        free_half = int(0.5 * torch.cuda.mem_get_info(dev)[0])
+        if self.workspace_budget is None:
+            budget, hard = DEFAULT_WORKSPACE_BUDGET, free_half
+        else:
+            budget = hard = min(self.workspace_budget, free_half)
+        return self._launch(dev, d, m, nh, 1, budget, hard, np.float64, (labels_nh, inertia, n_iter), f64,
+                            grid=grid)

@@ -26,7 +26,8 @@
  *   cc_kmeans_wide        the same for wide rows (d > 128), as distance/centre GEMM rounds
  *                         (sklearn KMeans: k-means++ init, Lloyd, best of n_init)
  *   cc_kmeans_f64         the same at float64 for float64 input
- *   cc_kmeans_fit         CC.py:282 in one call (plans and launches one of the three above)
+ *   cc_kmeans_launch_plan which of the three above a fit launches, how often and how large
+ *   cc_kmeans_fit         CC.py:282 in one call (makes the calls of cc_kmeans_launch_plan)
  *   cc_euclidean, cc_hc_gather, cc_hc_nnchain_batched, cc_hc_cut
  *                         CC.py:282 for AgglomerativeClustering (ward / average / complete,
  *                         euclidean): one tree per resample, cut at every K
@@ -375,10 +376,51 @@ size_t cc_prepare_rows_scratch_bytes(int n, int d);
 int cc_prepare_rows(const float* X, int n, int d, int dpad, float* Xd, float* xnorm, uint16_t* Xhl,
                     int* scale_exp, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Feature padding of the float32 engines' row image: 32 / 64 / 128 (cc_kmeans_batched), else the
+ * next multiple of 32 (cc_kmeans_wide).  Negative for d <= 0. */
+int cc_kmeans_dpad(int d);
+
+/* *e = the operand scale exponent of cc_split_f16 for max|X| = amax: the largest e in [-62, 62]
+ * with amax * 2^e <= 2^14 (0 for amax = 0).  CC_ERR_ARG when amax is not finite. */
+int cc_scale_exponent(float amax, int* e);
+
+/* One engine call of a fit, as cc_kmeans_launch_plan plans it. */
+#define CC_KM_ENGINE_BATCHED 0 /* cc_kmeans_batched */
+#define CC_KM_ENGINE_WIDE 1    /* cc_kmeans_wide */
+#define CC_KM_ENGINE_F64 2     /* cc_kmeans_f64 */
+typedef struct {
+  int32_t engine;    /* CC_KM_ENGINE_* */
+  int32_t k0, nk;    /* the call fits Ks[k0 .. k0 + nk) */
+  int32_t par;       /* batched, f64: `grid` workgroups; wide: `batch` resamples at once */
+  int32_t n_sub;     /* batched: units come from cc_kmeans_plan(Ks, nK, n_init, n_sub, ...); else 0 */
+  int32_t seedmax;   /* batched: concurrent seeders; else 0 */
+  uint64_t ws_bytes; /* engine workspace of the call */
+} cc_km_call;
+
+/* What is launched for the k-means of nh resamples of m rows with d features: the engine calls
+ * in order, written to calls[0 .. max_calls) (nK entries always suffice).  Returns their number
+ * (> 0) or a negative error.  Host arithmetic only: it touches no device, so the caller supplies
+ * the CU count and the byte budgets.
+ *  precision    CC_KM_FAST: one cc_kmeans_batched call (d <= 128) or the cc_kmeans_wide calls
+ *               that cc_kmeans_wide_chunk deals; CC_KM_F64: cc_kmeans_f64 calls of <= 64 K values
+ *  budget       engine workspace to stay within where the fit loses no speed by it; clipped to
+ *  budget_hard  the bytes never to exceed.  The batched grid starts at min(cus, units) and halves
+ *               until it fits the budget; a wide call runs the resamples in equal batches that
+ *               fit the budget; an f64 call takes the largest grid <= min(4 cus, nh * nk) that
+ *               fits max(budget, the bytes of two workgroups per CU) and budget_hard.  No rule
+ *               goes below one workgroup or one resample: compare ws_bytes with what you have.
+ *  n_sub, seedmax, grid  overrides (0: none) of the units per resample and the concurrent seeders
+ *               of the batched call (seedmax is still capped at 32 and the largest unit) and of
+ *               the f64 starting grid */
+int cc_kmeans_launch_plan(int d, int m, int nh, const int32_t* Ks, int nK, int n_init, int precision,
+                          int cus, size_t budget, size_t budget_hard, int n_sub, int seedmax, int grid,
+                          cc_km_call* calls, int max_calls);
+
 /* Every (resample h in [h_begin, h_end), K, init) k-means fit of a consensus fit in one call:
  * the loop of clusterer.fit_predict(X[indices]) at CC.py:282 for the default KMeans(n_init)
- * clusterer.  Plans units, grid and seedmax, builds the k-means++ tables and the row image, and
- * runs cc_kmeans_batched (d <= 128), cc_kmeans_wide (d > 128) or cc_kmeans_f64.
+ * clusterer.  Builds the k-means++ tables and the row image and makes the calls of
+ * cc_kmeans_launch_plan for this device and the workspace that is left (budget = budget_hard):
+ * cc_kmeans_batched (d <= 128), cc_kmeans_wide (d > 128) or cc_kmeans_f64.
  *  X        device [n][d] raw rows: float32 (CC_KM_FAST) or float64 (CC_KM_F64)
  *  idx_hm   device [H][m] int32 resample rows (rows outside [h_begin, h_end) are not read)
  *  Ks       host [nK], 1 <= K <= min(127, m)

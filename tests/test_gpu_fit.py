@@ -22,7 +22,8 @@ def _blobs(n, d, k, seed, dtype):
     return (C[rng.integers(0, k, n)] + rng.normal(size=(n, d))).astype(dtype)
 
 
-def _fit_abi(X, Ks, H, m, h0, h1, idx_d, precision, seed=3):
+def _fit_abi(X, Ks, H, m, h0, h1, idx_d, precision, seed=3, ws=None, wsb=None):
+    """cc_kmeans_fit in a workspace of its own query's size, or in the first wsb bytes of ws."""
     dev = idx_d.device
     n, d = X.shape
     Xd = torch.from_numpy(X).to(dev)
@@ -32,11 +33,13 @@ def _fit_abi(X, Ks, H, m, h0, h1, idx_d, precision, seed=3):
     nit = torch.zeros((len(Ks), H), dtype=torch.int32, device=dev)
     Ks_np = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
     lib = _lib.load()
-    wsb = lib.cc_kmeans_fit_workspace_bytes(n, d, m, h1 - h0, Ks_np.ctypes.data, len(Ks), 3, precision)
-    ws = torch.empty(int(wsb) or (1 << 20), dtype=torch.uint8, device=dev)
+    if ws is None:
+        wsb = lib.cc_kmeans_fit_workspace_bytes(n, d, m, h1 - h0, Ks_np.ctypes.data, len(Ks), 3, precision)
+        ws = torch.empty(int(wsb) or (1 << 20), dtype=torch.uint8, device=dev)
+        wsb = ws.numel()
     _lib.call("cc_kmeans_fit", Xd.data_ptr(), n, d, idx_d.data_ptr(), H, m, h0, h1, Ks_np.ctypes.data,
               len(Ks), 3, 300, 1e-4, ctypes.c_uint32(seed), precision, L.data_ptr(), L.stride(1),
-              inert.data_ptr(), nit.data_ptr(), ws.data_ptr(), ws.numel(), engine.stream_ptr(dev))
+              inert.data_ptr(), nit.data_ptr(), ws.data_ptr(), int(wsb), engine.stream_ptr(dev))
     torch.cuda.synchronize()
     return L, inert, nit
 
@@ -83,6 +86,43 @@ def test_one_call_matches_advanced_api(n, d, Ks, H, h0, h1, precision):
     lab = a[0][:, :, :H].cpu().numpy()
     assert (lab[:, :, :h0] == 0xFF).all() and (lab[:, :, h1:H] == 0xFF).all()
     assert (lab[:, :, h0:h1] != 0xFF).sum() == len(Ks) * (h1 - h0) * m
+
+
+@pytest.mark.parametrize("n,d,Ks,H,precision", [
+    (600, 16, [2, 5, 9], 6, 0),    # cc_kmeans_batched: one workgroup pulls every unit
+    (400, 300, [2, 4], 4, 0),      # cc_kmeans_wide: one resample per batch
+    (400, 12, [2, 3, 6], 6, 1),    # cc_kmeans_f64: one workgroup, a launch per resample
+])
+def test_tight_workspace_runs_the_smallest_plan(n, d, Ks, H, precision):
+    """A workspace with room for just the planner's smallest plan (budget = 1: one workgroup, one
+    resample per wide batch): cc_kmeans_fit plans into it, gives bit-identical results, writes
+    nothing past it, and rejects one byte less."""
+    from consensus_clustering_amd.kmeans import UNLIMITED, launch_plan
+
+    dev = engine.require_gpu()
+    X = _blobs(n, d, 5, seed=n + d, dtype=np.float64 if precision == 1 else np.float32)
+    m = int(0.8 * n)
+    idx_d = torch.from_numpy(engine.resample_indices(11, n, m, 0, H)).to(dev)
+    roomy = _fit_abi(X, Ks, H, m, 0, H, idx_d, precision)
+
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    align256 = lambda b: (b + 255) & ~255
+    most = max(c["ws_bytes"] for c in launch_plan(d, m, H, Ks, 3, precision, cus, UNLIMITED, UNLIMITED))
+    least = max(c["ws_bytes"] for c in launch_plan(d, m, H, Ks, 3, precision, cus, 1, 1))
+    Ks_np = np.asarray(Ks, dtype=np.int32)
+    full = _lib.load().cc_kmeans_fit_workspace_bytes(n, d, m, H, Ks_np.ctypes.data, len(Ks), 3, precision)
+    tight = full - align256(most) + align256(least)
+    assert 0 < tight < full
+
+    buf = torch.full((tight + (1 << 16),), 0x5A, dtype=torch.uint8, device=dev)  # workspace, then guard
+    got = _fit_abi(X, Ks, H, m, 0, H, idx_d, precision, ws=buf, wsb=tight)
+    for x, y in zip(got, roomy):
+        assert torch.equal(x, y)
+    assert bool((buf[tight:] == 0x5A).all())
+    with pytest.raises(_lib.CCMIError, match="workspace too small"):
+        _fit_abi(X, Ks, H, m, 0, H, idx_d, precision, ws=buf, wsb=tight - 1)
+    torch.cuda.synchronize()
+    assert bool((buf[tight:] == 0x5A).all())
 
 
 def test_one_call_rejects_bad_k():

@@ -128,17 +128,35 @@ def test_plan_rejects_unsupported():
 
 
 def test_choose_subsets_fills_the_grid():
-    assert kmeans.choose_subsets(1000, 19, 256) == 1
-    s = kmeans.choose_subsets(125, 19, 256)  # 8 GPUs at C3: 125 resamples per GPU
+    def choose_subsets(nh, n_groups, cus):  # the planner's rule, read off its batched call
+        call, = kmeans.launch_plan(16, 1000, nh, range(2, 2 + n_groups), 3, 0, cus, kmeans.UNLIMITED,
+                                   kmeans.UNLIMITED)
+        return call["n_sub"]
+
+    assert choose_subsets(1000, 19, 256) == 1
+    s = choose_subsets(125, 19, 256)  # 8 GPUs at C3: 125 resamples per GPU
     assert 125 * s >= 0.85 * 256
-    assert kmeans.choose_subsets(4, 3, 256) == 3
+    assert choose_subsets(4, 3, 256) == 3
 
 
 def test_scale_exponent():
-    assert kmeans.scale_exponent(0.0) == 0
+    import ctypes
+
+    from consensus_clustering_amd import _lib
+
+    def scale_exponent(amax):
+        e = ctypes.c_int(99)
+        _lib.call("cc_scale_exponent", amax, ctypes.byref(e))
+        return e.value
+
+    assert scale_exponent(0.0) == 0
     for amax in (1e-3, 0.7, 1.0, 3.0, 1e4, 6e4):
-        e = kmeans.scale_exponent(amax)
+        e = scale_exponent(amax)
+        amax = float(np.float32(amax))  # the library takes max|X| as the float32 it is on the device
         assert amax * 2.0 ** e <= 2 ** 14 and amax * 2.0 ** (e + 1) > 2 ** 14
+    for bad in (np.inf, -np.inf, np.nan):
+        with pytest.raises(_lib.CCMIError, match="non-finite"):
+            scale_exponent(bad)
 
 
 @pytest.mark.parametrize("m,dtype", [(23, np.float64), (8001, np.float32), (40000, np.float32),
