@@ -11,8 +11,9 @@ What runs where (``fit``):
                   cc_resample_device_wide) or on host threads (cc_resample_indices)
   clustering      default clusterer (KMeans) -> all (h, K, init) problems in batched
                   gfx950 launches (cc_kmeans_batched); AgglomerativeClustering (ward /
-                  average / complete, euclidean) -> one dendrogram per resample on the
-                  device, cut at every K (cc_euclidean, cc_hc_nnchain_batched,
+                  average / complete, euclidean; average / complete also with
+                  manhattan, cosine, correlation) -> one dendrogram per resample on the
+                  device, cut at every K (cc_euclidean / cc_pdist, cc_hc_nnchain_batched,
                   cc_hc_cut; ``hierarchical``); any other plugin clusterer
                   (e.g. GaussianMixture) keeps the reference's host fit_predict per
                   (K, h) and only its labels go to the GPU (hybrid path)
@@ -71,10 +72,17 @@ def _is_default_kmeans(est) -> bool:
 HC_LINKAGES = ('ward', 'average', 'complete')
 
 
-def _hc_linkage(est):
-    """The linkage of an AgglomerativeClustering that the device trees reproduce (cc_euclidean,
-    cc_hc_nnchain_batched, cc_hc_cut), else None: exactly that type, linkage ward / average /
-    complete, the euclidean metric, no connectivity and no distance threshold."""
+HC_METRICS = dict(euclidean='euclidean', l2='euclidean', manhattan='cityblock', l1='cityblock',
+                  cityblock='cityblock', cosine='cosine', correlation='correlation')
+
+
+def _hc_spec(est):
+    """(linkage, metric) of an AgglomerativeClustering that the device trees reproduce (cc_euclidean
+    / cc_pdist, cc_hc_nnchain_batched, cc_hc_cut), else None: exactly that type, linkage ward /
+    average / complete, no connectivity and no distance threshold.  The metric is scipy's name
+    for sklearn's spelling: 'euclidean' ('l2'), 'cityblock' ('manhattan', 'l1'), 'cosine' or
+    'correlation'.  Ward goes with euclidean alone (sklearn refuses the rest at fit time, so the
+    host path raises its message)."""
     try:
         from sklearn.cluster import AgglomerativeClustering
     except ImportError:  # pragma: no cover
@@ -86,16 +94,68 @@ def _hc_linkage(est):
     if not isinstance(link, str) or link not in HC_LINKAGES:
         return None
     metric = p.get("metric", "euclidean")
-    if not (metric is None or (isinstance(metric, str) and metric in ("euclidean", "l2"))):
+    if metric is None:
+        metric = "euclidean"
+    if not isinstance(metric, str) or metric not in HC_METRICS:
+        return None
+    metric = HC_METRICS[metric]
+    if link == "ward" and metric != "euclidean":
         return None
     if p.get("connectivity") is not None or p.get("distance_threshold") is not None:
         return None
-    return link
+    return link, metric
+
+
+def _hc_linkage(est):
+    """The linkage of an AgglomerativeClustering that the *euclidean* device trees reproduce
+    (cc_euclidean, cc_hc_nnchain_batched, cc_hc_cut), else None: _hc_spec with the euclidean
+    metric."""
+    spec = _hc_spec(est)
+    return spec[0] if spec is not None and spec[1] == "euclidean" else None
 
 
 def _is_device_hierarchical(est) -> bool:
-    """AgglomerativeClustering configured so that the device trees reproduce it."""
+    """AgglomerativeClustering configured so that the *euclidean* device trees reproduce it."""
     return _hc_linkage(est) is not None
+
+
+def _hc_degenerate(X, metric):
+    """Why pdist(X, metric) has a row without distances, or None, from the host array X: an
+    all-zero row under cosine (sklearn's own refusal, in its words) and a constant row under
+    correlation (it centres to zero, so its distances are 0 / 0)."""
+    if metric == "cosine":
+        if np.any(~np.any(X, axis=1)):
+            return "Cosine affinity cannot be used when X contains zero vectors"
+    elif metric == "correlation":
+        const = np.flatnonzero((X == X[:, :1]).all(axis=1))
+        if const.size:
+            return (f"the correlation metric cannot be used when X contains constant rows (row {int(const[0])} "
+                    "is constant: its correlation distances are undefined)")
+    return None
+
+
+def _hc_route(spec, X, hierarchical):
+    """The (linkage, metric) the device trees run, or None for the host loop, from the estimator's
+    _hc_spec, the host array X and the ``hierarchical`` keyword; decided from host values alone,
+    so every rank decides alike before any launch.  A degenerate row (_hc_degenerate) sends an
+    'auto' fit to the host loop, where sklearn raises only if a resample contains the row, and
+    is a ValueError under 'device', like an estimator the device does not reproduce."""
+    if hierarchical == 'host':
+        return None
+    if spec is None:
+        if hierarchical == 'device':
+            raise ValueError("hierarchical='device' needs clusterer=AgglomerativeClustering with linkage "
+                             "'ward' (euclidean metric), 'average' or 'complete' (metric 'euclidean', "
+                             "'manhattan', 'cosine' or 'correlation'), no connectivity and no "
+                             "distance_threshold")
+        return None
+    # X is read for these two metrics alone (for the others it may be a device tensor)
+    why = _hc_degenerate(np.asarray(X), spec[1]) if spec[1] in ('cosine', 'correlation') else None
+    if why is not None:
+        if hierarchical == 'device':
+            raise ValueError(why)
+        return None
+    return spec
 
 
 def _hc_validate(X, m, Ks):
@@ -173,7 +233,8 @@ class ConsensusClustering:
         # cc_resample_device_wide above), 'host' (native threads, then uploaded), 'auto' =
         # device; identical draws
         self.resampling = resampling
-        # an AgglomerativeClustering base clusterer (ward / average / complete, euclidean): 'auto'
+        # an AgglomerativeClustering base clusterer (ward / average / complete, euclidean; average /
+        # complete also with the manhattan, cosine and correlation metrics): 'auto'
         # = one tree per resample on the device when the estimator is one the device reproduces,
         # 'device' = the same but an error when it is not, 'host' = sklearn's fit_predict per (K, h)
         self.hierarchical = hierarchical
@@ -243,7 +304,7 @@ class ConsensusClustering:
         # new label matrix and indices reuse that memory instead of growing the pool by a set
         self.labels_ = self._idx_dev = self._idx_host = None
         self.kmeans_inertia_ = self.kmeans_n_iter_ = self.kmeans_stats_ = None
-        self.hc_stats_ = None
+        self.hc_stats_ = self.hc_metric_ = None
         if self.hierarchical not in ('auto', 'device', 'host'):
             raise ValueError("hierarchical must be 'auto', 'device' or 'host'")
         self.partial_ = False
@@ -292,11 +353,16 @@ class ConsensusClustering:
 
         km = self._kmeans_params()
         # the estimator as _kmeans_params left it: clusterer_options applied
-        hc = _hc_linkage(self.clusterer) if (Ks and km is None and self.hierarchical != 'host') else None
-        if self.hierarchical == 'device' and hc is None:
-            raise ValueError("hierarchical='device' needs clusterer=AgglomerativeClustering with linkage "
-                             "'ward', 'average' or 'complete', the euclidean metric, no connectivity and "
-                             "no distance_threshold")
+        hc = None
+        if Ks and km is None:
+            spec = _hc_spec(self.clusterer)
+            if spec is not None and spec[1] in ('cosine', 'correlation') and isinstance(X, torch.Tensor):
+                Xh = X.detach().cpu().numpy()  # the degenerate-row test reads host values
+            else:
+                Xh = X  # read only when a cosine / correlation estimator is routed
+            hc = _hc_route(spec, Xh, self.hierarchical)
+        elif self.hierarchical == 'device':
+            _hc_route(None, None, 'device')
         self.backend_ = 'gpu-kmeans' if km is not None else ('gpu-hc' if hc is not None else 'host-clusterer')
         precision = self.precision
         if precision == 'auto':
@@ -327,7 +393,8 @@ class ConsensusClustering:
                        scale_exp=sexp)
             self.kmeans_stats_ = bk.stats
         elif Ks and hc is not None:
-            self.hc_stats_ = self._fit_hierarchical(X, wdtype, hc, idx_d, n, m, h0, h1, Ks, labels, dev)
+            self.hc_metric_ = hc[1]
+            self.hc_stats_ = self._fit_hierarchical(X, wdtype, hc[0], hc[1], idx_d, n, m, h0, h1, Ks, labels, dev)
         elif Ks:
             if isinstance(X, torch.Tensor):
                 X = X.cpu().numpy()
@@ -390,10 +457,12 @@ class ConsensusClustering:
             self._plot_cdf()
         return self
 
-    def _fit_hierarchical(self, X, wdtype, link, idx_d, n, m, h0, h1, Ks, labels, dev):
-        """CC.py:282 for AgglomerativeClustering(linkage=link) on the device: the n x n euclidean
-        distances once (each rank its own), then one tree per resample of [h0, h1), cut at every
-        K, into this rank's columns of the label matrix."""
+    def _fit_hierarchical(self, X, wdtype, link, metric, idx_d, n, m, h0, h1, Ks, labels, dev):
+        """CC.py:282 for AgglomerativeClustering(linkage=link, metric=metric) on the device: the
+        n x n distances once (each rank its own; cc_euclidean, or cc_pdist for 'cityblock',
+        'cosine' and 'correlation'), then one tree per resample of [h0, h1), cut at every K, into
+        this rank's columns of the label matrix.  Under 'correlation' a device tensor X is copied
+        to the host, where numpy centres its rows as scipy does (engine.pdist)."""
         if isinstance(X, torch.Tensor):
             # a device tensor: the finiteness test runs where X lives (torch, no kernel of ours)
             _hc_validate(None if bool(torch.isfinite(X).all()) else X.detach().cpu().numpy(), m, Ks)
@@ -404,10 +473,12 @@ class ConsensusClustering:
         budget = self.workspace_budget
         if budget is not None:
             engine.hc_plan(n, m, max(h1 - h0, 1), len(Ks), budget)  # too small: raises before any launch
-        Dfull = engine.euclidean(Xd)
+        Dfull = engine.euclidean(Xd) if metric == 'euclidean' else engine.pdist(Xd, metric)
         if not bool(torch.isfinite(Dfull).all()):  # finite X can still overflow the squares
-            raise ValueError("the euclidean distances between the rows of X are not all finite "
-                             "(overflow in float64)")
+            if metric == 'euclidean':
+                raise ValueError("the euclidean distances between the rows of X are not all finite "
+                                 "(overflow in float64)")
+            raise ValueError(f"the {metric} distances between the rows of X are not all finite")
         return engine.hc_labels(Dfull, idx_d, h0, h1, Ks, link, labels, budget=budget)
 
     def _check_k_range(self, Ks):

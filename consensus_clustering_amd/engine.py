@@ -395,6 +395,36 @@ def euclidean(X: torch.Tensor) -> torch.Tensor:
     return D
 
 
+PDIST_METRICS = {"euclidean": 0, "cityblock": 1, "cosine": 2, "correlation": 2}  # CC_METRIC_* (include/ccmi.h)
+
+
+def pdist(X, metric: str) -> torch.Tensor:
+    """float64 [n, n] on the device: squareform(scipy.spatial.distance.pdist(X, metric)) bit for
+    bit, for the float32 or float64 rows X [n, d] and metric in PDIST_METRICS (cc_pdist).
+
+    'correlation' is scipy's own two steps: the rows less their means, X - X.mean(axis=1,
+    keepdims=True) on the float64 copy of X, computed by numpy on the host (its mean is a pairwise
+    sum, which the cosine code then sees rounded as numpy rounds it), then the cosine kernel on the
+    float64 upload.  A device tensor X is therefore copied to the host for this metric; a numpy
+    array is accepted for it too."""
+    if metric not in PDIST_METRICS:
+        raise ValueError(f"metric must be one of {sorted(PDIST_METRICS)}, got {metric!r}")
+    if metric == "correlation":
+        dev = X.device if isinstance(X, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+        Xh = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
+        Xh = np.ascontiguousarray(Xh, dtype=np.float64)
+        X = torch.from_numpy(np.ascontiguousarray(Xh - Xh.mean(axis=1, keepdims=True))).to(dev)
+    assert X.dim() == 2 and X.is_cuda and X.is_contiguous() and X.dtype in (torch.float32, torch.float64)
+    n, d = X.shape
+    D = torch.empty((n, n), dtype=torch.float64, device=X.device)
+    code = PDIST_METRICS[metric]
+    norms = torch.empty(n, dtype=torch.float64, device=X.device) if code == 2 else None
+    with timed("cc_pdist"):
+        _lib.call("cc_pdist", X.data_ptr(), int(X.dtype == torch.float64), n, d, code, D.data_ptr(),
+                  _lib.ptr(norms), stream_ptr(X.device))
+    return D
+
+
 def hc_gather(Dfull: torch.Tensor, idx_bm: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
     """float64 [B, m, m]: out[b] = Dfull[idx[b]][:, idx[b]] (cc_hc_gather)."""
     assert Dfull.dtype == torch.float64 and Dfull.dim() == 2 and Dfull.is_contiguous()

@@ -31,6 +31,8 @@
  *   cc_euclidean, cc_hc_gather, cc_hc_nnchain_batched, cc_hc_cut
  *                         CC.py:282 for AgglomerativeClustering (ward / average / complete,
  *                         euclidean): one tree per resample, cut at every K
+ *   cc_pdist              the distances of the same trees for metric = manhattan / cosine /
+ *                         correlation (average and complete linkage): scipy's pdist, bit for bit
  */
 #ifndef CCMI_H
 #define CCMI_H
@@ -221,6 +223,25 @@ int cc_linkage_check(const void* workspace, size_t ws_bytes, void* stream);
  * float64 sum over k, in increasing k, of (u_k - v_k)^2 with no FMA; symmetric, zero diagonal.
  * X [n][d] float32 (is_f64 = 0; converted exactly) or float64 (is_f64 = 1). */
 int cc_euclidean(const void* X, int is_f64, int n, int d, double* D, void* stream);
+
+/* The same matrix for the base clusterer's other metrics (AgglomerativeClustering(linkage =
+ * average | complete, metric = manhattan | cosine | correlation) -> scipy linkage(X, method,
+ * metric)): D [n][n] float64 = squareform(pdist(X, metric)) bit for bit, symmetric, exact-zero
+ * diagonal; X as for cc_euclidean.
+ *   CC_METRIC_EUCLIDEAN  cc_euclidean
+ *   CC_METRIC_CITYBLOCK  the float64 sum over k, in increasing k, of |u_k - v_k|
+ *   CC_METRIC_COSINE     1 - c, c = t(u, v) / (norm_u norm_v) with |c| > 1 clipped to +-1, where
+ *                        t is scipy's two-accumulator dot product: the products of even k and of
+ *                        odd k < (d & ~1) summed apart, in increasing k, then added, then the
+ *                        product of an odd last column added; norm_u = sqrt(t(u, u)), written to
+ *                        norms [n] (device, float64) by a pre-kernel.  A zero row gives NaN.
+ * pdist's 'correlation' is CC_METRIC_COSINE on the float64 rows less their means
+ * (X - X.mean(axis=1, keepdims=True) in numpy, whose mean is a pairwise sum): the caller centres.
+ * norms may be NULL for the other metrics.  An unknown metric returns CC_ERR_ARG. */
+#define CC_METRIC_EUCLIDEAN 0
+#define CC_METRIC_CITYBLOCK 1
+#define CC_METRIC_COSINE 2
+int cc_pdist(const void* X, int is_f64, int n, int d, int metric, double* D, double* norms, void* stream);
 
 /* Db [B][m][m]: Db[b][a][c] = Dfull[idx[b][a]][idx[b][c]] for B resamples (idx [B][m] int32,
  * values in [0, n)). */
