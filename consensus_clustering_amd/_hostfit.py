@@ -11,6 +11,12 @@ def fit_predict_one(clusterer, Xs):
     return np.asarray(clusterer.fit_predict(Xs))
 
 
+def subset(X, rows, cols=None):
+    """The rows of one resample, and under feature subsampling its columns, as the C-contiguous
+    array the clusterer is fitted on (X[rows][:, cols] alone is Fortran-ordered)."""
+    return X[rows] if cols is None else np.ascontiguousarray(X[rows][:, cols])
+
+
 def fit_predict_chunk(clusterer, Xs_list):
     """The labels of several resamples, one fit after the other on the task's own clusterer."""
     return [fit_predict_one(clusterer, Xs) for Xs in Xs_list]

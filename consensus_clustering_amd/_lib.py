@@ -64,6 +64,9 @@ SIGNATURES = {
     "cc_linkage_check": (_c_int, [_vp, ctypes.c_size_t, _vp]),
     "cc_euclidean": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp]),
     "cc_pdist": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
+    "cc_pdist_batched_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int, _c_int]),
+    "cc_pdist_batched": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp,
+                                  _vp, _c_sz, _vp]),
     "cc_hc_gather": (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _vp, _vp]),
     "cc_hc_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int]),
     "cc_hc_nnchain_batched": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _c_sz, _vp]),

@@ -14,7 +14,8 @@ What runs where (``fit``):
                   average / complete, euclidean; average / complete also with
                   manhattan, cosine, correlation) -> one dendrogram per resample on the
                   device, cut at every K (cc_euclidean / cc_pdist, cc_hc_nnchain_batched,
-                  cc_hc_cut; ``hierarchical``); any other plugin clusterer
+                  cc_hc_cut; ``hierarchical``), with ``feature_subsampling`` < 1 from each
+                  resample's own columns (cc_pdist_batched); any other plugin clusterer
                   (e.g. GaussianMixture) keeps the reference's host fit_predict per
                   (K, h) and only its labels go to the GPU (hybrid path)
   I, M, histogram int8-MFMA tiles of the upper triangle (cc_cosample / cc_coassoc)
@@ -43,7 +44,7 @@ import numpy as np
 import torch
 
 from . import dist, engine, post
-from ._hostfit import fit_predict_chunk, fit_predict_one
+from ._hostfit import fit_predict_chunk, fit_predict_one, subset
 from .kmeans import BatchedKMeans
 
 KMAX = 127  # largest K: uint8 labels (0xFF = not sampled) and int8 one-hot channels
@@ -134,12 +135,14 @@ def _hc_degenerate(X, metric):
     return None
 
 
-def _hc_route(spec, X, hierarchical):
+def _hc_route(spec, X, hierarchical, degenerate_test=True):
     """The (linkage, metric) the device trees run, or None for the host loop, from the estimator's
     _hc_spec, the host array X and the ``hierarchical`` keyword; decided from host values alone,
     so every rank decides alike before any launch.  A degenerate row (_hc_degenerate) sends an
     'auto' fit to the host loop, where sklearn raises only if a resample contains the row, and
-    is a ValueError under 'device', like an estimator the device does not reproduce."""
+    is a ValueError under 'device', like an estimator the device does not reproduce.
+    degenerate_test=False (feature subsampling, where the device route tests every resample's own
+    rows under its own columns) leaves that test out, and X unread."""
     if hierarchical == 'host':
         return None
     if spec is None:
@@ -150,7 +153,8 @@ def _hc_route(spec, X, hierarchical):
                              "distance_threshold")
         return None
     # X is read for these two metrics alone (for the others it may be a device tensor)
-    why = _hc_degenerate(np.asarray(X), spec[1]) if spec[1] in ('cosine', 'correlation') else None
+    why = (_hc_degenerate(np.asarray(X), spec[1]) if degenerate_test and spec[1] in ('cosine', 'correlation')
+           else None)
     if why is not None:
         if hierarchical == 'device':
             raise ValueError(why)
@@ -205,6 +209,7 @@ class ConsensusClustering:
         precision='auto',
         resampling='auto',
         hierarchical='auto',
+        feature_subsampling=1.0,
     ):
         self.K_range = K_range
         self.n_iterations = n_iterations
@@ -238,6 +243,12 @@ class ConsensusClustering:
         # = one tree per resample on the device when the estimator is one the device reproduces,
         # 'device' = the same but an error when it is not, 'host' = sklearn's fit_predict per (K, h)
         self.hierarchical = hierarchical
+        # the fraction of X's columns each resample sees (ConsensusClusterPlus's pFeature):
+        # md = int(feature_subsampling * d) of them, drawn per resample (post.feature_indices);
+        # 1.0 = every column, no draw.  The device trees compute each resample's distances from
+        # its columns (cc_pdist_batched); the k-means engines do not subsample features, so the
+        # default KMeans then runs in the host loop
+        self.feature_subsampling = feature_subsampling
         self.timings_ = {}
         self._rehearsal = None  # (rank, world): bench tooling only, see fit()
 
@@ -285,7 +296,7 @@ class ConsensusClustering:
         else:
             X = np.asarray(X)
             wdtype = X.dtype if X.dtype in (np.float32, np.float64) else np.float64
-        self._N, _ = X.shape
+        self._N, d = X.shape
         self._dtype = np.uint8 if self.n_iterations < 256 else np.uint16
         self.cdf_at_K_data = dict()
         n, H = self._N, int(self.n_iterations)
@@ -299,6 +310,11 @@ class ConsensusClustering:
             raise TypeError("unsupported operand type(s) for +: 'NoneType' and 'int'")
         if H > 0 and (int(self.random_state) < 0 or int(self.random_state) + H - 1 > 2**32 - 1):
             raise ValueError("Seed must be between 0 and 2**32 - 1")
+        # the feature fraction, refused from host values on every rank before any launch or exchange
+        md = self._feature_count(d)
+        self.feature_indices_ = cols = None
+        if md < d:
+            self.feature_indices_ = cols = post.feature_indices(self.random_state, d, md, H)
         rank, W = dist.world()
         # a refit replaces the previous results: their device buffers are dropped first, so the
         # new label matrix and indices reuse that memory instead of growing the pool by a set
@@ -352,9 +368,17 @@ class ConsensusClustering:
         t_rs = time.perf_counter()
 
         km = self._kmeans_params()
+        if km is not None and cols is not None:
+            warnings.warn("the k-means engines do not subsample features: with feature_subsampling < 1 the "
+                          "KMeans fits run on the host (sklearn, one fit per resample and K)", UserWarning)
+            km = None
         # the estimator as _kmeans_params left it: clusterer_options applied
         hc = None
-        if Ks and km is None:
+        if Ks and km is None and cols is not None:
+            # each resample's own rows decide (engine.hc_labels finds a row without distances
+            # under the resample's columns), so the whole-X test of _hc_route is not asked
+            hc = _hc_route(_hc_spec(self.clusterer), None, self.hierarchical, degenerate_test=False)
+        elif Ks and km is None:
             spec = _hc_spec(self.clusterer)
             if spec is not None and spec[1] in ('cosine', 'correlation') and isinstance(X, torch.Tensor):
                 Xh = X.detach().cpu().numpy()  # the degenerate-row test reads host values
@@ -394,7 +418,8 @@ class ConsensusClustering:
             self.kmeans_stats_ = bk.stats
         elif Ks and hc is not None:
             self.hc_metric_ = hc[1]
-            self.hc_stats_ = self._fit_hierarchical(X, wdtype, hc[0], hc[1], idx_d, n, m, h0, h1, Ks, labels, dev)
+            self.hc_stats_ = self._fit_hierarchical(X, wdtype, hc[0], hc[1], idx_d, n, m, h0, h1, Ks, labels, dev,
+                                                    cols=cols)
         elif Ks:
             if isinstance(X, torch.Tensor):
                 X = X.cpu().numpy()
@@ -404,7 +429,8 @@ class ConsensusClustering:
                 self._K = K
                 self._set_clusterer_K()
                 lab = host_fit_predict(self.clusterer, X, idx[h0:h1], self.n_jobs,
-                                       self.parallelization_method)
+                                       self.parallelization_method,
+                                       cols=None if cols is None else cols[h0:h1])
                 if lab.size and (lab.min() < 0 or lab.max() >= K):
                     raise ValueError(f"clusterer labels must lie in [0, {K})")
                 engine.scatter_labels(idx_d[h0:h1].contiguous(), torch.from_numpy(lab).to(dev), n,
@@ -457,12 +483,30 @@ class ConsensusClustering:
             self._plot_cdf()
         return self
 
-    def _fit_hierarchical(self, X, wdtype, link, metric, idx_d, n, m, h0, h1, Ks, labels, dev):
+    def _feature_count(self, d):
+        """md = int(feature_subsampling * d), the same truncation as the item count; a bool, a
+        fraction outside (0, 1] or md < 1 is a ValueError that names the value and d."""
+        f = self.feature_subsampling
+        ok = not isinstance(f, (bool, np.bool_)) and isinstance(f, (int, float, np.integer, np.floating))
+        if ok:
+            ok = 0 < f <= 1 and int(f * d) >= 1
+        if not ok:
+            raise ValueError(f"feature_subsampling must be a fraction in (0, 1] that keeps at least one of the "
+                             f"d = {d} features (int(feature_subsampling * d) >= 1), got {f!r}")
+        return int(f * d)
+
+    def _fit_hierarchical(self, X, wdtype, link, metric, idx_d, n, m, h0, h1, Ks, labels, dev, cols=None):
         """CC.py:282 for AgglomerativeClustering(linkage=link, metric=metric) on the device: the
         n x n distances once (each rank its own; cc_euclidean, or cc_pdist for 'cityblock',
         'cosine' and 'correlation'), then one tree per resample of [h0, h1), cut at every K, into
         this rank's columns of the label matrix.  Under 'correlation' a device tensor X is copied
-        to the host, where numpy centres its rows as scipy does (engine.pdist)."""
+        to the host, where numpy centres its rows as scipy does (engine.pdist).
+
+        cols (int32 [H, md], feature subsampling): no n x n matrix; every resample's distances
+        come from its own columns (cc_pdist_batched, which centres on the device, so a device
+        tensor X stays there for every metric).  A resample that holds a row without distances
+        under its columns raises ValueError, as sklearn does in the host loop; the ranks agree on
+        the lowest such resample before the label exchange (dist.first_failure), so all raise."""
         if isinstance(X, torch.Tensor):
             # a device tensor: the finiteness test runs where X lives (torch, no kernel of ours)
             _hc_validate(None if bool(torch.isfinite(X).all()) else X.detach().cpu().numpy(), m, Ks)
@@ -471,6 +515,21 @@ class ConsensusClustering:
             _hc_validate(X, m, Ks)
             Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=wdtype)).to(dev)
         budget = self.workspace_budget
+        if cols is not None:
+            md = cols.shape[1]
+            if budget is not None:
+                engine.hc_plan(n, m, max(h1 - h0, 1), len(Ks), budget, md=md)  # too small: raises before any launch
+            cols_d = torch.from_numpy(cols).to(dev)
+            stats = code = None
+            try:
+                stats = engine.hc_labels(None, idx_d, h0, h1, Ks, link, labels, budget=budget, X=Xd,
+                                         cols_d=cols_d, metric=metric)
+            except engine.DegenerateResample as e:
+                code = e.code
+            code = dist.first_failure(code, dev)
+            if code is not None:
+                raise engine.DegenerateResample(code, metric)
+            return stats
         if budget is not None:
             engine.hc_plan(n, m, max(h1 - h0, 1), len(Ks), budget)  # too small: raises before any launch
         Dfull = engine.euclidean(Xd) if metric == 'euclidean' else engine.pdist(Xd, metric)
@@ -732,9 +791,11 @@ def _fit_predict_one(clusterer, Xs):
     return fit_predict_one(clusterer, Xs)
 
 
-def host_fit_predict(clusterer, X, idx, n_jobs=1, parallelization_method='multithreading'):
+def host_fit_predict(clusterer, X, idx, n_jobs=1, parallelization_method='multithreading', cols=None):
     """int32 labels [len(idx), m] of ``clusterer.fit_predict(X[idx[h]])`` for every resample h
     (CC.py:282), the hybrid path's host stage for a clusterer the GPU k-means does not replace.
+    cols: optional int [len(idx), md], the feature subset of each resample (feature subsampling);
+    resample h is then fitted on the C-contiguous copy of ``X[idx[h]][:, cols[h]]``.
 
     n_jobs == 1: one call after the other on the clusterer itself (CC.py:180-183).  Otherwise the
     resamples fan out over joblib workers as CC.py:185-195 does: threads for
@@ -757,15 +818,19 @@ def host_fit_predict(clusterer, X, idx, n_jobs=1, parallelization_method='multit
     if H == 0:
         m = idx.shape[1] if getattr(idx, 'ndim', 1) == 2 else 0
         return np.empty((0, m), dtype=np.int32)
+
+    def sub(h):
+        return subset(X, idx[h], None if cols is None else cols[h])
+
     if n_jobs == 1:
-        return np.stack([_fit_predict_one(clusterer, X[i]) for i in idx]).astype(np.int32)
+        return np.stack([_fit_predict_one(clusterer, sub(h)) for h in range(H)]).astype(np.int32)
     from joblib import Parallel, delayed, effective_n_jobs, parallel_config
 
     if parallelization_method not in ('multithreading', 'multiprocessing'):
         raise RuntimeError(f'unknown parallelization method: {parallelization_method}')
     if parallelization_method == 'multithreading' and not _picklable(clusterer):
         out = Parallel(n_jobs=n_jobs, prefer='threads')(
-            delayed(fit_predict_one)(_clone(clusterer), X[i]) for i in idx)
+            delayed(fit_predict_one)(_clone(clusterer), sub(h)) for h in range(H))
     else:
         chunks = max(1, min(H, 4 * effective_n_jobs(n_jobs)))
         bounds = np.linspace(0, H, chunks + 1).astype(int)
@@ -774,7 +839,7 @@ def host_fit_predict(clusterer, X, idx, n_jobs=1, parallelization_method='multit
         # 16-CPU share measured 7x slower than the serial loop)
         with parallel_config(backend='loky', inner_max_num_threads=1):
             parts = Parallel(n_jobs=n_jobs)(
-                delayed(fit_predict_chunk)(clusterer, [X[i] for i in idx[a:b]])
+                delayed(fit_predict_chunk)(clusterer, [sub(h) for h in range(a, b)])
                 for a, b in zip(bounds[:-1], bounds[1:]) if b > a)
         out = [lab for part in parts for lab in part]
     return np.stack(out).astype(np.int32)

@@ -125,6 +125,22 @@ def sum_counts(t: torch.Tensor) -> torch.Tensor:
     return _all_reduce(t, dist.ReduceOp.SUM)
 
 
+def first_failure(code, device=None):
+    """The smallest ``code`` any rank reports, or None when no rank reports one: a MIN all-reduce
+    of one int64 (None travels as the largest int64).  A condition that only the rank owning a
+    resample can see (a resample without distances under its feature subset) is agreed on here,
+    before the label exchange, so that every rank raises the same error instead of one rank
+    leaving the others in a collective.  ``code`` is a non-negative int; does nothing without a
+    process group."""
+    if not _exchange():
+        return code
+    none = torch.iinfo(torch.int64).max
+    t = torch.tensor([none if code is None else int(code)], dtype=torch.int64, device=device)
+    _all_reduce(t, dist.ReduceOp.MIN)
+    got = int(t.item())
+    return None if got == none else got
+
+
 def barrier():
     if _live() and dist.get_world_size() > 1:
         dist.barrier()

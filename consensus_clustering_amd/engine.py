@@ -425,6 +425,91 @@ def pdist(X, metric: str) -> torch.Tensor:
     return D
 
 
+# CC_METRIC_* of cc_pdist_batched, which centres the rows for 'correlation' itself
+PDIST_BATCHED_METRICS = {"euclidean": 0, "cityblock": 1, "cosine": 2, "correlation": 3}
+
+
+def _pdist_batched(X, idx_bm, cols_bq, metric, out=None):
+    """pdist_batched, and with the distances the norms [B, m] the row pass wrote (cosine and
+    correlation; None otherwise)."""
+    if metric not in PDIST_BATCHED_METRICS:
+        raise ValueError(f"metric must be one of {sorted(PDIST_BATCHED_METRICS)}, got {metric!r}")
+    assert X.dim() == 2 and X.is_cuda and X.is_contiguous() and X.dtype in (torch.float32, torch.float64)
+    assert idx_bm.dtype == torch.int32 and idx_bm.dim() == 2 and idx_bm.is_contiguous() and idx_bm.is_cuda
+    assert cols_bq.dtype == torch.int32 and cols_bq.dim() == 2 and cols_bq.is_contiguous() and cols_bq.is_cuda
+    n, d = X.shape
+    B, m = idx_bm.shape
+    md = cols_bq.shape[1]
+    if cols_bq.shape[0] != B or B < 1 or m < 1 or md < 1:
+        raise ValueError("idx must be [B, m] and cols [B, md] with B, m and md at least 1")
+    # an entry outside its range would be read out of bounds by the row pass: checked here, on
+    # the device tensors, before anything is launched
+    lo, hi = (int(v) for v in torch.aminmax(idx_bm))
+    if lo < 0 or hi >= n:
+        raise ValueError(f"idx entries must lie in [0, {n}), got [{lo}, {hi}]")
+    lo, hi = (int(v) for v in torch.aminmax(cols_bq))
+    if lo < 0 or hi >= d:
+        raise ValueError(f"cols entries must lie in [0, {d}), got [{lo}, {hi}]")
+    code = PDIST_BATCHED_METRICS[metric]
+    if out is None:
+        out = torch.empty((B, m, m), dtype=torch.float64, device=X.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == B * m * m
+    ws = torch.empty(int(_lib.load().cc_pdist_batched_workspace_bytes(B, m, md, code)) // 8, dtype=torch.float64,
+                     device=X.device)
+    with timed("cc_pdist_batched"):
+        _lib.call("cc_pdist_batched", X.data_ptr(), int(X.dtype == torch.float64), n, d, idx_bm.data_ptr(),
+                  cols_bq.data_ptr(), B, m, md, code, out.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                  stream_ptr(X.device))
+    return out.view(B, m, m), (ws[B * m * md:].view(B, m) if code >= 2 else None)
+
+
+def pdist_batched(X: torch.Tensor, idx_bm: torch.Tensor, cols_bq: torch.Tensor, metric: str,
+                  out: torch.Tensor = None) -> torch.Tensor:
+    """float64 [B, m, m] on the device: out[b] = squareform(scipy.spatial.distance.pdist(
+    X[idx[b]][:, cols[b]], metric)) bit for bit (cc_pdist_batched), for the float32 or float64
+    rows X [n, d], the int32 rows idx [B, m] and ascending columns cols [B, md] of B resamples and
+    metric in PDIST_BATCHED_METRICS; 'correlation' is centred on the device.  An idx or cols entry
+    out of range raises ValueError before the launch."""
+    return _pdist_batched(X, idx_bm, cols_bq, metric, out)[0]
+
+
+DEGENERATE_ZERO_NORM, DEGENERATE_NOT_FINITE = 0, 1
+
+
+class DegenerateResample(ValueError):
+    """A resample has a row without distances under its feature subset, or distances that are
+    not finite.  code = 4 * h + kind (DEGENERATE_*): the smallest code over the ranks names the
+    lowest such resample (dist.first_failure)."""
+
+    def __init__(self, code: int, metric: str):
+        self.code, self.metric = int(code), metric
+        h, kind = divmod(self.code, 4)
+        if kind == DEGENERATE_ZERO_NORM and metric == "cosine":
+            why = "Cosine affinity cannot be used when X contains zero vectors"
+        elif kind == DEGENERATE_ZERO_NORM:
+            why = "a row is constant, so its correlation distances are undefined"
+        else:
+            why = "the distances are not all finite"
+        super().__init__(f"{why} (resample {h}, metric {metric!r}, on the resample's feature subset)")
+
+
+def _degenerate_code(D: torch.Tensor, norms, h_first: int):
+    """The DegenerateResample code of the first tree of a batch (D [B, m, m], norms [B, m] or
+    None, tree b = resample h_first + b) that has a zero norm or a distance that is not finite,
+    else None.  One pass over the batch and one device-to-host read of two flags per tree: a NaN
+    or an infinity anywhere in a tree reaches the tree's sum; a tree whose finite distances
+    overflow the sum is told apart by the exact test, which runs for flagged trees alone."""
+    bad = ~torch.isfinite(D.flatten(1).sum(dim=1))
+    zero = (norms == 0).any(dim=1) if norms is not None else torch.zeros_like(bad)
+    flags = torch.stack([zero, bad]).cpu().numpy()
+    for b in np.flatnonzero(flags.any(axis=0)):
+        if flags[0, b]:
+            return 4 * (int(h_first) + int(b)) + DEGENERATE_ZERO_NORM
+        if not bool(torch.isfinite(D[b]).all()):
+            return 4 * (int(h_first) + int(b)) + DEGENERATE_NOT_FINITE
+    return None
+
+
 def hc_gather(Dfull: torch.Tensor, idx_bm: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
     """float64 [B, m, m]: out[b] = Dfull[idx[b]][:, idx[b]] (cc_hc_gather)."""
     assert Dfull.dtype == torch.float64 and Dfull.dim() == 2 and Dfull.is_contiguous()
@@ -490,39 +575,70 @@ def hc_tree_bytes(m: int, nK: int) -> int:
     return 8 * m * m + (32 + 8 + 8 + 4) * (m - 1) + 8 * m + 4 * nK * m + 512  # 512: status word, alignment
 
 
-def hc_plan(n: int, m: int, nh: int, nK: int, budget: int):
+def hc_feature_bytes(m: int, md: int) -> int:
+    """Device bytes one tree of a batch needs on top of hc_tree_bytes under feature subsampling:
+    its compact float64 rows [m, md], their norms and its column indices."""
+    return 8 * int(m) * int(md) + 8 * int(m) + 4 * int(md)
+
+
+def hc_plan(n: int, m: int, nh: int, nK: int, budget: int, md: int = None):
     """(B, route) for the nh resamples of a rank: B = min(nh, (budget - 8 n^2) // bytes per tree)
     trees per launch; route 'batched' (cc_hc_nnchain_batched on B trees) or 'sequential' (one
     tree at a time through cc_linkage_nnchain, grid form for large m) when the budget holds fewer
     trees than HC_BATCH_CROSSOVER and fewer than the rank has.  Raises when the n x n distances
-    and one tree do not fit the budget."""
+    and one tree do not fit the budget.
+
+    md (feature subsampling: every tree computes its own distances from md columns,
+    cc_pdist_batched): there is no n x n matrix, so the budget holds no 8 n^2 term, and a tree
+    needs hc_feature_bytes(m, md) more."""
     per = hc_tree_bytes(m, nK)
-    fit = (int(budget) - 8 * int(n) * int(n)) // per
-    if fit < 1:
-        raise ValueError(
-            f"workspace_budget = {int(budget)} bytes cannot hold the hierarchical clusterer: the n x n "
-            f"float64 distances ({8 * int(n) * int(n)} bytes) and one tree of m = {int(m)} "
-            f"({per} bytes) are needed")
+    if md is not None:
+        per += hc_feature_bytes(m, md)
+        fit = int(budget) // per
+        if fit < 1:
+            raise ValueError(
+                f"workspace_budget = {int(budget)} bytes cannot hold the hierarchical clusterer: one tree "
+                f"of m = {int(m)} over {int(md)} features ({per} bytes) is needed")
+    else:
+        fit = (int(budget) - 8 * int(n) * int(n)) // per
+        if fit < 1:
+            raise ValueError(
+                f"workspace_budget = {int(budget)} bytes cannot hold the hierarchical clusterer: the n x n "
+                f"float64 distances ({8 * int(n) * int(n)} bytes) and one tree of m = {int(m)} "
+                f"({per} bytes) are needed")
     B = max(1, min(int(nh), int(fit)))
     route = 'sequential' if B < min(int(nh), HC_BATCH_CROSSOVER) else 'batched'
     return B, route
 
 
 def hc_labels(Dfull: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, method: str,
-              labels: torch.Tensor, budget: int = None, route: str = 'auto') -> dict:
+              labels: torch.Tensor, budget: int = None, route: str = 'auto', X: torch.Tensor = None,
+              cols_d: torch.Tensor = None, metric: str = None) -> dict:
     """Fill labels[k, idx[h, r], h] for h in [h0, h1) and every K of Ks with the K-cluster cut of
     the `method` tree over Dfull[idx[h]][:, idx[h]] (AgglomerativeClustering.fit_predict of every
     (h, K), one tree per h).  idx_d: int32 [H, m] on the device.  budget: device bytes for Dfull
     and the trees (default: half the free memory plus Dfull, which exists already).  Returns the
-    plan that ran: dict(route, batch, launches)."""
-    n = Dfull.shape[0]
+    plan that ran: dict(route, batch, launches).
+
+    Feature subsampling: Dfull None, and X [n, d] (device), cols_d int32 [H, md] (device, indexed
+    by the global h like idx_d) and `metric` instead.  Tree h is then built over
+    pdist(X[idx[h]][:, cols[h]], metric), computed per batch (cc_pdist_batched); budget: device
+    bytes for the trees alone (default: half the free memory).  A resample with a row without
+    distances under its columns, or with distances that are not finite, raises
+    DegenerateResample for the first such h of the range, before that batch's trees."""
+    feature = Dfull is None
+    if feature:
+        if X is None or cols_d is None or metric is None:
+            raise ValueError("without Dfull, hc_labels needs X, cols_d and metric")
+        n, dev, md = X.shape[0], X.device, cols_d.shape[1]
+    else:
+        n, dev, md = Dfull.shape[0], Dfull.device, None
     m = idx_d.shape[1]
     nh = h1 - h0
-    dev = Dfull.device
     nK = len(Ks)
     if budget is None:
-        budget = 8 * n * n + torch.cuda.mem_get_info(dev)[0] // 2
-    B, planned = hc_plan(n, m, max(nh, 1), nK, budget)
+        budget = (0 if feature else 8 * n * n) + torch.cuda.mem_get_info(dev)[0] // 2
+    B, planned = hc_plan(n, m, max(nh, 1), nK, budget, md=md)
     if route == 'auto':
         route = planned
     if route not in ('batched', 'sequential'):
@@ -530,6 +646,8 @@ def hc_labels(Dfull: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, me
     if route == 'sequential':
         B = 1
     stats = dict(route=route, batch=B, launches=0)
+    if feature:
+        stats['feature_subsampling'] = md
     if nh <= 0 or nK == 0:
         return stats
     Ks_d = torch.tensor([int(K) for K in Ks], dtype=torch.int32, device=dev)
@@ -538,7 +656,13 @@ def hc_labels(Dfull: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, me
     for a in range(h0, h1, B):
         b = min(a + B, h1)
         rows = idx_d[a:b].contiguous()
-        D = hc_gather(Dfull, rows, out=Db[:b - a])
+        if feature:
+            D, norms = _pdist_batched(X, rows, cols_d[a:b].contiguous(), metric, out=Db[:b - a])
+            code = _degenerate_code(D, norms, a)
+            if code is not None:
+                raise DegenerateResample(code, metric)
+        else:
+            D = hc_gather(Dfull, rows, out=Db[:b - a])
         if route == 'batched':
             Z = hc_nnchain_batched(D, method, ws)
         else:

@@ -79,6 +79,19 @@ def best_k(pac: dict):
     return Ks[int(np.argmin(np.array([pac[K] for K in Ks], dtype=np.float64)))]
 
 
+def feature_indices(random_state, d: int, md: int, H: int) -> np.ndarray:
+    """int32 [H, md]: the columns resample h sees under feature subsampling,
+    ``sort(RandomState((random_state + h, 1)).choice(d, md, replace=False))``.  The array seed
+    keeps this stream apart from the item stream ``RandomState(random_state + h)``; sorted, a
+    subset keeps X's column order, which is the summation order of its distances.  Host numpy,
+    O(H d)."""
+    out = np.empty((int(H), int(md)), dtype=np.int32)
+    for h in range(int(H)):
+        rs = np.random.RandomState((int(random_state) + h, 1))
+        out[h] = np.sort(rs.choice(int(d), int(md), replace=False))
+    return out
+
+
 def linkage_finish(Z, n):
     """scipy linkage()'s last steps on nn_chain's raw merges Z [n-1, 4] (x, y, distance, size in
     merge order): a stable sort by distance, then label() (scipy/cluster/_hierarchy.pyx): with a

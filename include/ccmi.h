@@ -33,6 +33,8 @@
  *                         euclidean): one tree per resample, cut at every K
  *   cc_pdist              the distances of the same trees for metric = manhattan / cosine /
  *                         correlation (average and complete linkage): scipy's pdist, bit for bit
+ *   cc_pdist_batched      the same distances per resample when each resample also draws its own
+ *                         columns (feature subsampling): pdist(X[idx[b]][:, cols[b]], metric)
  */
 #ifndef CCMI_H
 #define CCMI_H
@@ -242,6 +244,23 @@ int cc_euclidean(const void* X, int is_f64, int n, int d, double* D, void* strea
 #define CC_METRIC_CITYBLOCK 1
 #define CC_METRIC_COSINE 2
 int cc_pdist(const void* X, int is_f64, int n, int d, int metric, double* D, double* norms, void* stream);
+
+/* Feature subsampling: the distances of B resamples that each draw their own rows AND columns.
+ * Db [B][m][m] float64: Db[b] = squareform(pdist(X[idx[b]][:, cols[b]], metric)) bit for bit,
+ * symmetric, exact-zero diagonal.  X [n][d] as for cc_euclidean; idx [B][m] int32 in [0, n);
+ * cols [B][md] int32 in [0, d), ascending (their order is the summation order); all on the device.
+ * The caller checks both ranges: an entry outside them is read out of bounds.
+ * metric: CC_METRIC_EUCLIDEAN, _CITYBLOCK, _COSINE, or CC_METRIC_CORRELATION, which this entry
+ * point alone accepts: a row pass writes each resample's compact float64 rows [B][m][md] into
+ * the workspace, for correlation less numpy's mean of the compact row (s / md, s numpy's pairwise
+ * sum), and for cosine and correlation scipy's norms [B][m] behind them (a norm of 0 marks a row
+ * without distances); a tile pass then runs the arithmetic of cc_pdist / cc_euclidean per tree.
+ * CC_ERR_ARG: a null pointer, a size below 1, md > d, m > n, B > 65535, an unknown metric, or
+ * fewer workspace bytes than cc_pdist_batched_workspace_bytes (0 for arguments it refuses). */
+#define CC_METRIC_CORRELATION 3
+size_t cc_pdist_batched_workspace_bytes(int B, int m, int md, int metric);
+int cc_pdist_batched(const void* X, int is_f64, int n, int d, const int* idx, const int* cols, int B, int m,
+                     int md, int metric, double* Db, void* workspace, size_t ws_bytes, void* stream);
 
 /* Db [B][m][m]: Db[b][a][c] = Dfull[idx[b][a]][idx[b][c]] for B resamples (idx [B][m] int32,
  * values in [0, n)). */
