@@ -3,11 +3,8 @@
 // Monti's paper), on the device.
 //
 // sklearn hands such an estimator to scipy.cluster.hierarchy.linkage(X, method, 'euclidean') and
-// cuts the tree with _hc_cut.  Four kernels restate that chain:
-//   euclid_kernel   pdist(X, 'euclidean') as a full symmetric float64 [n][n]: sqrt of the float64
-//                   sum over k, in increasing k, of (u_k - v_k)^2, no FMA (scipy's
-//                   distance_impl.h); the value of a pair does not depend on the resample, so
-//                   the fit computes it once
+// cuts the tree with _hc_cut.  The distances pdist(X, metric) come from pdist.hip, as one full
+// symmetric float64 [n][n] a fit or one [m][m] a resample; three kernels restate the rest:
 //   gather_kernel   the distances of resample b: D_b[a][c] = Dfull[idx[b][a]][idx[b][c]]
 //   nnchain_batched scipy's nn_chain, one workgroup per tree, with the decisions of predict.hip's
 //                   nnchain_kernel (linkage_shared.hpp); workgroups never communicate
@@ -31,88 +28,6 @@
 #pragma clang fp contract(off)  // every product and sum of this file is rounded separately
 
 namespace {
-
-// ---- euclidean distances: 64 x 64 output tiles of the upper triangle (mirrored), 256 threads as
-// 16 x 16, each thread 4 x 4 float64 accumulators; k slabs of 16 of both row blocks staged in LDS
-// as float64 ([k][row]: a thread reads its 4 rows and 4 columns with two 16-B pairs each).  Every
-// output is one sequential sum over k in increasing order.
-constexpr int ET = 64;  // tile edge
-constexpr int EK = 16;  // k slab
-constexpr int ER = 4;   // accumulators per thread and side
-
-template <typename T>
-__global__ __launch_bounds__(256) void euclid_kernel(const T* __restrict__ X, int n, int d,
-                                                     double* __restrict__ D) {
-  const int nb = (n + ET - 1) / ET;
-  int t = static_cast<int>(blockIdx.x), bi = 0;
-  while (t >= nb - bi) {  // blockIdx.x enumerates the upper-triangle tiles row-major
-    t -= nb - bi;
-    ++bi;
-  }
-  const int bj = bi + t;
-  __shared__ __attribute__((aligned(16))) double sa[EK][ET];
-  __shared__ __attribute__((aligned(16))) double sb[EK][ET];
-  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-  const int i0 = bi * ET, j0 = bj * ET;
-  double acc[ER][ER];
-#pragma unroll
-  for (int r = 0; r < ER; ++r)
-#pragma unroll
-    for (int c = 0; c < ER; ++c) acc[r][c] = 0.0;
-  // staging: thread tid loads 4 consecutive k of row tid >> 2, per side (rows past n and k past d
-  // read as 0: they add (0 - 0)^2 to nothing that is stored, or are never summed)
-  const int sr = tid >> 2, sk = 4 * (tid & 3);
-  for (int k0 = 0; k0 < d; k0 += EK) {
-    double ga[4], gb[4];
-    const int gi = i0 + sr, gj = j0 + sr;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int gk = k0 + sk + q;
-      ga[q] = (gi < n && gk < d) ? static_cast<double>(X[static_cast<int64_t>(gi) * d + gk]) : 0.0;
-      gb[q] = (gj < n && gk < d) ? static_cast<double>(X[static_cast<int64_t>(gj) * d + gk]) : 0.0;
-    }
-    __syncthreads();  // the previous slab's reads are done
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      sa[sk + q][sr] = ga[q];
-      sb[sk + q][sr] = gb[q];
-    }
-    __syncthreads();
-    const int kn = min(EK, d - k0);
-    for (int k = 0; k < kn; ++k) {
-      double a[ER], b[ER];
-#pragma unroll
-      for (int q = 0; q < ER; q += 2) {
-        const double2 av = *reinterpret_cast<const double2*>(&sa[k][ER * ty + q]);
-        const double2 bv = *reinterpret_cast<const double2*>(&sb[k][ER * tx + q]);
-        a[q] = av.x;
-        a[q + 1] = av.y;
-        b[q] = bv.x;
-        b[q + 1] = bv.y;
-      }
-#pragma unroll
-      for (int r = 0; r < ER; ++r)
-#pragma unroll
-        for (int c = 0; c < ER; ++c) {
-          const double df = a[r] - b[c];
-          acc[r][c] += df * df;
-        }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < ER; ++r)
-#pragma unroll
-    for (int c = 0; c < ER; ++c) {
-      const int i = i0 + ER * ty + r, j = j0 + ER * tx + c;
-      // a diagonal tile holds both (i, j) and (j, i): each thread stores its own entry alone
-      // ((u - v)^2 == (v - u)^2, so the two are equal); the others mirror theirs
-      if (i < n && j < n) {
-        const double v = __dsqrt_rn(acc[r][c]);
-        D[static_cast<int64_t>(i) * n + j] = v;
-        if (bi != bj) D[static_cast<int64_t>(j) * n + i] = v;
-      }
-    }
-}
 
 __global__ __launch_bounds__(256) void gather_kernel(const double* __restrict__ Dfull, int n,
                                                      const int* __restrict__ idx, int m,
@@ -332,27 +247,6 @@ int launch_error(const char* what) {
 }
 
 }  // namespace
-
-extern "C" int cc_euclidean(const void* X, int is_f64, int n, int d, double* D, void* stream) {
-  if (!X || !D || n <= 0 || d <= 0) {
-    cc::set_error("cc_euclidean: bad arguments");
-    return CC_ERR_ARG;
-  }
-  const int64_t nb = (n + ET - 1) / ET;
-  const int64_t tiles = nb * (nb + 1) / 2;
-  if (tiles > 0x7fffffff) {
-    cc::set_error("cc_euclidean: n too large");
-    return CC_ERR_ARG;
-  }
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  if (is_f64)
-    hipLaunchKernelGGL(euclid_kernel<double>, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, st,
-                       static_cast<const double*>(X), n, d, D);
-  else
-    hipLaunchKernelGGL(euclid_kernel<float>, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, st,
-                       static_cast<const float*>(X), n, d, D);
-  return launch_error("cc_euclidean");
-}
 
 extern "C" int cc_hc_gather(const double* Dfull, int n, const int* idx, int B, int m, double* Db, void* stream) {
   if (!Dfull || !idx || !Db || n <= 0 || B <= 0 || m <= 0 || B > 65535 || m > 65535) {

@@ -395,7 +395,7 @@ def euclidean(X: torch.Tensor) -> torch.Tensor:
     return D
 
 
-PDIST_METRICS = {"euclidean": 0, "cityblock": 1, "cosine": 2, "correlation": 2}  # CC_METRIC_* (include/ccmi.h)
+PDIST_METRICS = {"euclidean": 0, "cityblock": 1, "cosine": 2, "correlation": 3}  # CC_METRIC_* (include/ccmi.h)
 
 
 def pdist(X, metric: str) -> torch.Tensor:
@@ -417,7 +417,8 @@ def pdist(X, metric: str) -> torch.Tensor:
     assert X.dim() == 2 and X.is_cuda and X.is_contiguous() and X.dtype in (torch.float32, torch.float64)
     n, d = X.shape
     D = torch.empty((n, n), dtype=torch.float64, device=X.device)
-    code = PDIST_METRICS[metric]
+    # the rows are centred by now, and cc_pdist knows no CC_METRIC_CORRELATION: cosine on them
+    code = PDIST_METRICS["cosine" if metric == "correlation" else metric]
     norms = torch.empty(n, dtype=torch.float64, device=X.device) if code == 2 else None
     with timed("cc_pdist"):
         _lib.call("cc_pdist", X.data_ptr(), int(X.dtype == torch.float64), n, d, code, D.data_ptr(),
@@ -425,15 +426,11 @@ def pdist(X, metric: str) -> torch.Tensor:
     return D
 
 
-# CC_METRIC_* of cc_pdist_batched, which centres the rows for 'correlation' itself
-PDIST_BATCHED_METRICS = {"euclidean": 0, "cityblock": 1, "cosine": 2, "correlation": 3}
-
-
 def _pdist_batched(X, idx_bm, cols_bq, metric, out=None):
     """pdist_batched, and with the distances the norms [B, m] the row pass wrote (cosine and
     correlation; None otherwise)."""
-    if metric not in PDIST_BATCHED_METRICS:
-        raise ValueError(f"metric must be one of {sorted(PDIST_BATCHED_METRICS)}, got {metric!r}")
+    if metric not in PDIST_METRICS:
+        raise ValueError(f"metric must be one of {sorted(PDIST_METRICS)}, got {metric!r}")
     assert X.dim() == 2 and X.is_cuda and X.is_contiguous() and X.dtype in (torch.float32, torch.float64)
     assert idx_bm.dtype == torch.int32 and idx_bm.dim() == 2 and idx_bm.is_contiguous() and idx_bm.is_cuda
     assert cols_bq.dtype == torch.int32 and cols_bq.dim() == 2 and cols_bq.is_contiguous() and cols_bq.is_cuda
@@ -450,7 +447,7 @@ def _pdist_batched(X, idx_bm, cols_bq, metric, out=None):
     lo, hi = (int(v) for v in torch.aminmax(cols_bq))
     if lo < 0 or hi >= d:
         raise ValueError(f"cols entries must lie in [0, {d}), got [{lo}, {hi}]")
-    code = PDIST_BATCHED_METRICS[metric]
+    code = PDIST_METRICS[metric]  # cc_pdist_batched centres the rows for correlation itself
     if out is None:
         out = torch.empty((B, m, m), dtype=torch.float64, device=X.device)
     assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == B * m * m
@@ -468,7 +465,7 @@ def pdist_batched(X: torch.Tensor, idx_bm: torch.Tensor, cols_bq: torch.Tensor, 
     """float64 [B, m, m] on the device: out[b] = squareform(scipy.spatial.distance.pdist(
     X[idx[b]][:, cols[b]], metric)) bit for bit (cc_pdist_batched), for the float32 or float64
     rows X [n, d], the int32 rows idx [B, m] and ascending columns cols [B, md] of B resamples and
-    metric in PDIST_BATCHED_METRICS; 'correlation' is centred on the device.  An idx or cols entry
+    metric in PDIST_METRICS; 'correlation' is centred on the device.  An idx or cols entry
     out of range raises ValueError before the launch."""
     return _pdist_batched(X, idx_bm, cols_bq, metric, out)[0]
 

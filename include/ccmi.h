@@ -230,7 +230,7 @@ int cc_euclidean(const void* X, int is_f64, int n, int d, double* D, void* strea
  * average | complete, metric = manhattan | cosine | correlation) -> scipy linkage(X, method,
  * metric)): D [n][n] float64 = squareform(pdist(X, metric)) bit for bit, symmetric, exact-zero
  * diagonal; X as for cc_euclidean.
- *   CC_METRIC_EUCLIDEAN  cc_euclidean
+ *   CC_METRIC_EUCLIDEAN  cc_euclidean (the same tile kernel, as for every metric here)
  *   CC_METRIC_CITYBLOCK  the float64 sum over k, in increasing k, of |u_k - v_k|
  *   CC_METRIC_COSINE     1 - c, c = t(u, v) / (norm_u norm_v) with |c| > 1 clipped to +-1, where
  *                        t is scipy's two-accumulator dot product: the products of even k and of
@@ -254,7 +254,7 @@ int cc_pdist(const void* X, int is_f64, int n, int d, int metric, double* D, dou
  * point alone accepts: a row pass writes each resample's compact float64 rows [B][m][md] into
  * the workspace, for correlation less numpy's mean of the compact row (s / md, s numpy's pairwise
  * sum), and for cosine and correlation scipy's norms [B][m] behind them (a norm of 0 marks a row
- * without distances); a tile pass then runs the arithmetic of cc_pdist / cc_euclidean per tree.
+ * without distances); the tile kernel of cc_pdist / cc_euclidean then runs once per tree.
  * CC_ERR_ARG: a null pointer, a size below 1, md > d, m > n, B > 65535, an unknown metric, or
  * fewer workspace bytes than cc_pdist_batched_workspace_bytes (0 for arguments it refuses). */
 #define CC_METRIC_CORRELATION 3

@@ -75,7 +75,7 @@ def _pw(a):
 
 
 def recipe_mean(row):
-    """numpy's mean of a float64 row as csrc/pdist_batched.hip restates it: from 0.0, the pairwise
+    """numpy's mean of a float64 row as csrc/pdist.hip restates it: from 0.0, the pairwise
     sum of each piece of numpy's buffer size added in turn; divided by the length."""
     row = [np.float64(x) for x in row]
     s = np.float64(0.0)
