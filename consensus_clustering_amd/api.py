@@ -10,7 +10,9 @@ What runs where (``fit``):
   resampling      numpy-RandomState replay on the device (libccmi cc_resample_device /
                   cc_resample_device_wide) or on host threads (cc_resample_indices)
   clustering      default clusterer (KMeans) -> all (h, K, init) problems in batched
-                  gfx950 launches (cc_kmeans_batched); AgglomerativeClustering (ward /
+                  gfx950 launches (cc_kmeans_batched; in float64 cc_kmeans_f64, which with
+                  ``feature_subsampling`` < 1 fits each resample on its own columns,
+                  cc_kmeans_f64_cols); AgglomerativeClustering (ward /
                   average / complete, euclidean; average / complete also with
                   manhattan, cosine, correlation) -> one dendrogram per resample on the
                   device, cut at every K (cc_euclidean / cc_pdist, cc_hc_nnchain_batched,
@@ -75,6 +77,26 @@ HC_LINKAGES = ('ward', 'average', 'complete')
 
 HC_METRICS = dict(euclidean='euclidean', l2='euclidean', manhattan='cityblock', l1='cityblock',
                   cityblock='cityblock', cosine='cosine', correlation='correlation')
+
+
+PRECISIONS = ('auto', 'f64', 'fast')
+
+
+def _kmeans_route(precision, wdtype, has_cols):
+    """Where the default KMeans runs: (resolved precision, on_device).  precision is the
+    constructor keyword (validated here, before it decides anything), wdtype the working dtype of
+    X (np.float32 or np.float64), has_cols whether feature subsampling drew a column list.
+
+    'auto' resolves by the input dtype as the reference's clusterer computes in X's dtype
+    (CC.py:282): float64 -> 'f64' (cc_kmeans_f64), float32 -> 'fast' (the f16 hi/lo MFMA engines).
+    Without columns both run on the device.  With columns only the float64 engine does
+    (cc_kmeans_f64_cols gathers each resample's columns in its setup); the float32-class engines
+    share one operand image of X across resamples, so 'fast' then keeps the host loop."""
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be 'auto', 'f64' or 'fast'")
+    if precision == 'auto':
+        precision = 'f64' if np.dtype(wdtype) == np.float64 else 'fast'
+    return precision, (not has_cols) or precision == 'f64'
 
 
 def _hc_spec(est):
@@ -246,8 +268,9 @@ class ConsensusClustering:
         # the fraction of X's columns each resample sees (ConsensusClusterPlus's pFeature):
         # md = int(feature_subsampling * d) of them, drawn per resample (post.feature_indices);
         # 1.0 = every column, no draw.  The device trees compute each resample's distances from
-        # its columns (cc_pdist_batched); the k-means engines do not subsample features, so the
-        # default KMeans then runs in the host loop
+        # its columns (cc_pdist_batched), the float64 k-means gathers them in its per-resample setup
+        # (cc_kmeans_f64_cols); the float32-class k-means engines do not subsample features, so
+        # the default KMeans at precision 'fast' then runs in the host loop (_kmeans_route)
         self.feature_subsampling = feature_subsampling
         self.timings_ = {}
         self._rehearsal = None  # (rank, world): bench tooling only, see fit()
@@ -368,9 +391,12 @@ class ConsensusClustering:
         t_rs = time.perf_counter()
 
         km = self._kmeans_params()
-        if km is not None and cols is not None:
+        if km is not None and cols is not None and not _kmeans_route(self.precision, wdtype, True)[1]:
+            # the float64 engine gathers each resample's columns (cc_kmeans_f64_cols); the
+            # float32-class engines share one operand image of X across resamples and do not
             warnings.warn("the k-means engines do not subsample features: with feature_subsampling < 1 the "
-                          "KMeans fits run on the host (sklearn, one fit per resample and K)", UserWarning)
+                          "KMeans fits run on the host (sklearn, one fit per resample and K) unless they run on "
+                          "the float64 engine (float64 input, or precision='f64')", UserWarning)
             km = None
         # the estimator as _kmeans_params left it: clusterer_options applied
         hc = None
@@ -407,9 +433,13 @@ class ConsensusClustering:
                 X64 = (X.to(dev, torch.float64) if isinstance(X, torch.Tensor)
                        else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(dev))
                 self.kmeans_inertia_ = torch.zeros((len(Ks), H), dtype=torch.float64, device=dev)
+                # feature subsampling: every rank holds all H column rows and runs its [h0, h1)
                 bk.run_f64(X64.contiguous(), idx_d, n, H, m, h0, h1, labels,
-                           inertia=self.kmeans_inertia_, n_iter=self.kmeans_n_iter_)
+                           inertia=self.kmeans_inertia_, n_iter=self.kmeans_n_iter_,
+                           cols_d=None if cols is None else torch.from_numpy(cols).to(dev))
             else:
+                if cols is not None:  # _kmeans_route keeps such a fit off these engines
+                    raise RuntimeError("the float32-class k-means engines take no column list")
                 Xd, xnorm, _, Xhl, sexp = _prepare(X, dev)
                 self.kmeans_inertia_ = torch.zeros((len(Ks), H), dtype=torch.float32, device=dev)
                 bk.run(Xd, xnorm, X.shape[1], idx_d, n, H, m, h0, h1, labels, weight_dtype=wdtype,

@@ -27,7 +27,9 @@
 // Each resample's centred rows, their fragment image, row norms and tol are built once, by two
 // setup kernels before the units' launch, into per-resample slots of the workspace (up to grid
 // resamples per launch); a unit of two adjacent K's (where units are plentiful) runs both K's
-// problems in one lockstep group.
+// problems in one lockstep group.  Only the setup kernels read X: under feature subsampling
+// (cc_kmeans_f64_cols) they gather each resample's own columns and the slots, and with them the
+// whole engine, have that subset's width.
 // Round 5: a unit's inits run in lockstep groups of up to GMAX (each pass over the rows - the
 // k-means++ distances, the E-step, the centre sums, the inertia - serves every running init of
 // the group; an init that converges leaves the group), and the centre sums accumulate in LDS
@@ -72,8 +74,8 @@ constexpr int F64_KPAIR_MAX = 127;  // only K's up to this are grouped
 constexpr int F64_UNITS_PER_WG = 2;  // ... and only with at least this many units per workgroup
 
 struct F64Args {
-  const double* X;  // [n][d] (not centred)
-  int n, d;
+  const double* X;  // [n][ldx] (not centred)
+  int n, d;         // d: the row width of every slot and of the engine (md under feature subsampling)
   const int32_t* idx;  // [H][m]
   int H, m, h_begin, nh;
   int nK;
@@ -98,6 +100,11 @@ struct F64Args {
   // per-resample images (slot hb of this launch's resamples), built once by the setup kernels
   char* rs;
   size_t per_res, r_mean, r_var, r_tol, r_xsq, r_xc, r_xf;
+  // feature subsampling (cc_kmeans_f64_cols; read by the setup kernels only, and appended so that
+  // every offset kmeans_f64_kernel reads stays where it was): resample h keeps the columns
+  // cols[h][0 .. d) of X's ldx; null: every column, ldx = d
+  const int32_t* cols;  // [H][d] ascending, or null
+  int ldx;              // row stride of X (its full width)
 };
 
 // numpy pairwise_sum (numpy/_core/src/umath/loops_utils.h.src) of a contiguous double array:
@@ -830,14 +837,14 @@ __device__ void kpp_pot0(const double* cl, int m, double* part, double* out, int
   __syncthreads();
 }
 
-// centred feature k of resample row r
-__device__ __forceinline__ double xc(const F64Args& a, const int32_t* idx, const double* mean, int r, int k) {
-  return a.X[static_cast<size_t>(idx[r]) * a.d + k] - mean[k];
-}
-
 // ---- per-resample setup (KMeans.fit's centring and _tolerance, once per resample) -----------
+// COLS (cc_kmeans_f64_cols): the resample's rows are X[idx[r]][cols[h][k]], k < d, of a matrix of
+// row stride ldx; the slot is laid out for those d columns and everything after the gather is the
+// plain path at that width.  Without COLS neither cols nor ldx is loaded.
+//
 // Thread (slot, feature k): the column mean of the resample's rows (rows in order), then the
 // variance of the centred column, the loads of 16 rows in flight ahead of the adds.
+template <bool COLS>
 __global__ __launch_bounds__(NT) void f64_setup_stats(const F64Args* __restrict__ pa) {
   const F64Args& a = *pa;
   const int d = a.d, m = a.m;
@@ -846,27 +853,30 @@ __global__ __launch_bounds__(NT) void f64_setup_stats(const F64Args* __restrict_
   const int hb = static_cast<int>(e / d), k = static_cast<int>(e - static_cast<long long>(hb) * d);
   const int32_t* idx = a.idx + static_cast<size_t>(a.h_begin + hb) * m;
   char* rb = a.rs + static_cast<size_t>(hb) * a.per_res;
+  // the thread's column of X and X's row stride (the column row is that of resample h_begin + hb)
+  const int ldx = COLS ? a.ldx : d;
+  const int c = COLS ? a.cols[static_cast<size_t>(a.h_begin + hb) * d + k] : k;
   double s = 0.0;
   int r = 0;
   for (; r + 16 <= m; r += 16) {
     double v[16];
 #pragma unroll
-    for (int u = 0; u < 16; ++u) v[u] = a.X[static_cast<size_t>(idx[r + u]) * d + k];
+    for (int u = 0; u < 16; ++u) v[u] = a.X[static_cast<size_t>(idx[r + u]) * ldx + c];
 #pragma unroll
     for (int u = 0; u < 16; ++u) s += v[u];
   }
-  for (; r < m; ++r) s += a.X[static_cast<size_t>(idx[r]) * d + k];
+  for (; r < m; ++r) s += a.X[static_cast<size_t>(idx[r]) * ldx + c];
   const double mu = s / m;
   double q = 0.0;
   for (r = 0; r + 16 <= m; r += 16) {
     double v[16];
 #pragma unroll
-    for (int u = 0; u < 16; ++u) v[u] = a.X[static_cast<size_t>(idx[r + u]) * d + k] - mu;
+    for (int u = 0; u < 16; ++u) v[u] = a.X[static_cast<size_t>(idx[r + u]) * ldx + c] - mu;
 #pragma unroll
     for (int u = 0; u < 16; ++u) q += v[u] * v[u];
   }
   for (; r < m; ++r) {
-    const double t = a.X[static_cast<size_t>(idx[r]) * d + k] - mu;
+    const double t = a.X[static_cast<size_t>(idx[r]) * ldx + c] - mu;
     q += t * t;
   }
   reinterpret_cast<double*>(rb + a.r_mean)[k] = mu;
@@ -880,11 +890,14 @@ constexpr int SRT = 4;  // row tiles of 16 per setup workgroup
 // holds row 16t + (l & 15), feature 4s + (l >> 4); exact zeros past m and d, so every operand
 // load of a k-step is one contiguous 512-B piece), the rows' squared norms (einsum order); block 0
 // also tol = mean(var) * tol_rel (_tolerance: numpy pairwise mean over the features).
+template <bool COLS>
 __global__ __launch_bounds__(NT) void f64_setup_rows(const F64Args* __restrict__ pa, int nrb) {
   const F64Args& a = *pa;
   const int d = a.d, m = a.m, tid = threadIdx.x;
   const int hb = blockIdx.x / nrb, rbk = blockIdx.x - hb * nrb;
   const int32_t* idx = a.idx + static_cast<size_t>(a.h_begin + hb) * m;
+  const int ldx = COLS ? a.ldx : d;
+  const int32_t* cols_h = COLS ? a.cols + static_cast<size_t>(a.h_begin + hb) * d : nullptr;
   char* rb = a.rs + static_cast<size_t>(hb) * a.per_res;
   const double* mean = reinterpret_cast<const double*>(rb + a.r_mean);
   double* xcp = reinterpret_cast<double*>(rb + a.r_xc);
@@ -896,8 +909,8 @@ __global__ __launch_bounds__(NT) void f64_setup_rows(const F64Args* __restrict__
   }
   const int r0 = rbk * SRT * 16, r1 = r0 + SRT * 16 < m ? r0 + SRT * 16 : m;
   for (int r = r0; r < r1; ++r) {
-    const double* xr = a.X + static_cast<size_t>(idx[r]) * d;
-    for (int k = tid; k < d; k += NT) xcp[static_cast<size_t>(r) * d + k] = xr[k] - mean[k];
+    const double* xr = a.X + static_cast<size_t>(idx[r]) * ldx;
+    for (int k = tid; k < d; k += NT) xcp[static_cast<size_t>(r) * d + k] = xr[COLS ? cols_h[k] : k] - mean[k];
   }
   __syncthreads();
   const int S4 = (d + 3) >> 2;
@@ -1399,6 +1412,7 @@ F64Layout f64_layout(int m, int d, int kmax) {
 
 constexpr size_t WS_ARGS = 64;  // the work counter at 0, the kernel's F64Args at WS_ARGS
 constexpr size_t WS_HEADER = (WS_ARGS + sizeof(F64Args) + 255) / 256 * 256;
+static_assert(WS_ARGS + sizeof(F64Args) <= WS_HEADER, "F64Args must fit the workspace header");
 
 }  // namespace
 
@@ -1430,39 +1444,40 @@ extern "C" size_t cc_kmeans_f64_workspace_bytes(int m, int d, const int32_t* Ks,
   return f64_ws_bytes(f64_layout(m, d, kmax), grid, nh);
 }
 
-extern "C" int cc_kmeans_f64(const double* X, int n, int d, const int32_t* idx_hm, int H, int m,
-                             int h_begin, int h_end, const int32_t* Ks, int nK, int n_init,
-                             int max_iter, double tol_rel, const double* kpp_u, int kpp_stride,
-                             const int32_t* kpp_pos, uint8_t* labels_nh, int ldl, double* inertia,
-                             int32_t* n_iter, void* workspace, size_t ws_bytes, int grid,
-                             void* stream) {
+// Both entry points: X [n][ldx]; cols null (every column, d = ldx) or device [H][d], the d columns
+// each resample keeps.  d is the row width of the slots, the workspace and the engine.
+static int f64_run(const std::string& fn, const double* X, int n, int ldx, const int32_t* cols, int d,
+                   const int32_t* idx_hm, int H, int m, int h_begin, int h_end, const int32_t* Ks, int nK,
+                   int n_init, int max_iter, double tol_rel, const double* kpp_u, int kpp_stride,
+                   const int32_t* kpp_pos, uint8_t* labels_nh, int ldl, double* inertia, int32_t* n_iter,
+                   void* workspace, size_t ws_bytes, int grid, void* stream) {
   if (!X || !idx_hm || !Ks || !kpp_u || !kpp_pos || !labels_nh || n <= 0 || d <= 0 || m <= 0 ||
       m > n || H <= 0 || h_begin < 0 || h_end > H || h_end < h_begin || nK <= 0 || nK > NKMAX ||
       n_init <= 0 || max_iter <= 0 || ldl < H || grid <= 0) {
-    cc::set_error("cc_kmeans_f64: bad arguments");
+    cc::set_error(fn + ": bad arguments");
     return CC_ERR_ARG;
   }
   if ((reinterpret_cast<uintptr_t>(X) & 7) != 0 || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
-    cc::set_error("cc_kmeans_f64: X must be 8-B and the workspace 16-B aligned");
+    cc::set_error(fn + ": X must be 8-B and the workspace 16-B aligned");
     return CC_ERR_ARG;
   }
   int kmax = 1;
   for (int i = 0; i < nK; ++i) {
     if (Ks[i] < 1 || Ks[i] > KMAX || Ks[i] > m) {
-      cc::set_error("cc_kmeans_f64: need 1 <= K <= min(127, m)");
+      cc::set_error(fn + ": need 1 <= K <= min(127, m)");
       return CC_ERR_ARG;
     }
     kmax = std::max(kmax, Ks[i]);
   }
   if (kpp_stride < cc::km::kpp_row_len(kmax)) {
-    cc::set_error("cc_kmeans_f64: kpp_stride too small");
+    cc::set_error(fn + ": kpp_stride too small");
     return CC_ERR_ARG;
   }
   const int nh = h_end - h_begin;
   if (nh == 0) return CC_OK;
   const F64Layout L = f64_layout(m, d, kmax);
   if (!workspace || ws_bytes < f64_ws_bytes(L, grid, nh)) {
-    cc::set_error("cc_kmeans_f64: workspace too small");
+    cc::set_error(fn + ": workspace too small");
     return CC_ERR_ARG;
   }
   const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1470,6 +1485,8 @@ extern "C" int cc_kmeans_f64(const double* X, int n, int d, const int32_t* idx_h
   a.X = X;
   a.n = n;
   a.d = d;
+  a.cols = cols;
+  a.ldx = ldx;
   a.idx = idx_hm;
   a.H = H;
   a.m = m;
@@ -1572,14 +1589,54 @@ extern "C" int cc_kmeans_f64(const double* X, int n, int d, const int32_t* idx_h
     hipError_t e = hipMemcpyAsync(workspace, header, sizeof(header), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
       const long long nst = (static_cast<long long>(cn) * d + NT - 1) / NT;
-      hipLaunchKernelGGL(f64_setup_stats, dim3(static_cast<unsigned>(nst)), dim3(NT), 0, st, pa);
-      hipLaunchKernelGGL(f64_setup_rows, dim3(static_cast<unsigned>(cn) * nrb), dim3(NT), 0, st, pa, nrb);
+      if (cols) {
+        hipLaunchKernelGGL(f64_setup_stats<true>, dim3(static_cast<unsigned>(nst)), dim3(NT), 0, st, pa);
+        hipLaunchKernelGGL(f64_setup_rows<true>, dim3(static_cast<unsigned>(cn) * nrb), dim3(NT), 0, st, pa, nrb);
+      } else {
+        hipLaunchKernelGGL(f64_setup_stats<false>, dim3(static_cast<unsigned>(nst)), dim3(NT), 0, st, pa);
+        hipLaunchKernelGGL(f64_setup_rows<false>, dim3(static_cast<unsigned>(cn) * nrb), dim3(NT), 0, st, pa, nrb);
+      }
       const unsigned blocks = static_cast<unsigned>(std::min<long long>(grid, static_cast<long long>(cn) * a.nuk));
       if (P * n_init > 4) hipLaunchKernelGGL(kmeans_f64_kernel<GMAX>, dim3(blocks), dim3(NT), 0, st, pa);
       else hipLaunchKernelGGL(kmeans_f64_kernel<4>, dim3(blocks), dim3(NT), 0, st, pa);
       e = hipGetLastError();
     }
-    if (e != hipSuccess) return cc::km::hip_fail("cc_kmeans_f64", e);
+    if (e != hipSuccess) return cc::km::hip_fail(fn, e);
   }
   return CC_OK;
+}
+
+extern "C" int cc_kmeans_f64(const double* X, int n, int d, const int32_t* idx_hm, int H, int m,
+                             int h_begin, int h_end, const int32_t* Ks, int nK, int n_init,
+                             int max_iter, double tol_rel, const double* kpp_u, int kpp_stride,
+                             const int32_t* kpp_pos, uint8_t* labels_nh, int ldl, double* inertia,
+                             int32_t* n_iter, void* workspace, size_t ws_bytes, int grid,
+                             void* stream) {
+  return f64_run("cc_kmeans_f64", X, n, d, nullptr, d, idx_hm, H, m, h_begin, h_end, Ks, nK, n_init, max_iter,
+                 tol_rel, kpp_u, kpp_stride, kpp_pos, labels_nh, ldl, inertia, n_iter, workspace, ws_bytes, grid,
+                 stream);
+}
+
+extern "C" int cc_kmeans_f64_cols(const double* X, int n, int d, const int32_t* cols_hmd, int md,
+                                  const int32_t* idx_hm, int H, int m, int h_begin, int h_end,
+                                  const int32_t* Ks, int nK, int n_init, int max_iter, double tol_rel,
+                                  const double* kpp_u, int kpp_stride, const int32_t* kpp_pos,
+                                  uint8_t* labels_nh, int ldl, double* inertia, int32_t* n_iter,
+                                  void* workspace, size_t ws_bytes, int grid, void* stream) {
+  if (!cols_hmd) {
+    cc::set_error("cc_kmeans_f64_cols: cols is null (cc_kmeans_f64 takes every column)");
+    return CC_ERR_ARG;
+  }
+  if (d <= 0 || md < 1 || md > d) {
+    cc::set_error("cc_kmeans_f64_cols: need 1 <= md <= d, got md = " + std::to_string(md) + ", d = " +
+                  std::to_string(d));
+    return CC_ERR_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(cols_hmd) & 3) != 0) {
+    cc::set_error("cc_kmeans_f64_cols: cols must be 4-B aligned");
+    return CC_ERR_ARG;
+  }
+  return f64_run("cc_kmeans_f64_cols", X, n, d, cols_hmd, md, idx_hm, H, m, h_begin, h_end, Ks, nK, n_init,
+                 max_iter, tol_rel, kpp_u, kpp_stride, kpp_pos, labels_nh, ldl, inertia, n_iter, workspace,
+                 ws_bytes, grid, stream);
 }

@@ -219,20 +219,39 @@ class BatchedKMeans:
                             int(0.6 * torch.cuda.mem_get_info(dev)[0]), weight_dtype, outputs, wide)
 
     def run_f64(self, X64, idx_d, n, H, m, h_begin, h_end, labels_nh, inertia=None, n_iter=None,
-                grid=None):
-        """float64 path (cc_kmeans_f64): X64 is the raw [n, d] float64 input on the device."""
+                grid=None, cols_d=None):
+        """float64 path (cc_kmeans_f64): X64 is the raw [n, d] float64 input on the device.
+
+        cols_d (feature subsampling, cc_kmeans_f64_cols): int32 [H, md] on X64's device, row h the
+        ascending columns resample h is fitted on.  The fit is then planned at row width md.  A
+        wrong dtype or shape and an entry outside [0, d), which the setup kernels would read out
+        of bounds, are refused here, from the device tensor, before anything is launched."""
         dev = X64.device
         if max(self.Ks) > m:
             raise ValueError(f"n_samples={m} should be >= n_clusters={max(self.Ks)}.")
+        d = width = X64.shape[1]
+        if cols_d is not None:
+            if not (isinstance(cols_d, torch.Tensor) and cols_d.dtype == torch.int32 and cols_d.device == dev):
+                raise ValueError("cols_d must be an int32 tensor on X's device")
+            if cols_d.dim() != 2 or cols_d.shape[0] != H or not 1 <= cols_d.shape[1] <= d:
+                raise ValueError(f"cols_d must be [H, md] = [{H}, 1 <= md <= {d}], got {list(cols_d.shape)}")
+            cols_d = cols_d.contiguous()
+            lo, hi = (int(v) for v in torch.aminmax(cols_d))
+            if lo < 0 or hi >= d:
+                raise ValueError(f"cols entries must lie in [0, {d}), got [{lo}, {hi}]")
+            width = cols_d.shape[1]
         self.stats = torch.zeros(128, dtype=torch.int64, device=dev)
         nh = h_end - h_begin
         if nh <= 0:
             return labels_nh
-        d = X64.shape[1]
 
         def f64(c, Ks, fit, ws):
-            _lib.call("cc_kmeans_f64", X64.data_ptr(), n, d, idx_d.data_ptr(), H, m, h_begin, h_end,
-                      Ks.ctypes.data, len(Ks), *fit, *ws, c["par"], engine.stream_ptr(dev))
+            rest = (idx_d.data_ptr(), H, m, h_begin, h_end, Ks.ctypes.data, len(Ks), *fit, *ws, c["par"],
+                    engine.stream_ptr(dev))
+            if cols_d is None:
+                _lib.call("cc_kmeans_f64", X64.data_ptr(), n, d, *rest)
+            else:
+                _lib.call("cc_kmeans_f64_cols", X64.data_ptr(), n, d, cols_d.data_ptr(), width, *rest)
 
         # never more than half the free device memory; the planner may exceed the DEFAULT budget up
         # to that to keep the kernel's occupancy, never a budget the caller set
@@ -241,5 +260,5 @@ class BatchedKMeans:
             budget, hard = DEFAULT_WORKSPACE_BUDGET, free_half
         else:
             budget = hard = min(self.workspace_budget, free_half)
-        return self._launch(dev, d, m, nh, 1, budget, hard, np.float64, (labels_nh, inertia, n_iter), f64,
+        return self._launch(dev, width, m, nh, 1, budget, hard, np.float64, (labels_nh, inertia, n_iter), f64,
                             grid=grid)

@@ -26,6 +26,7 @@
  *   cc_kmeans_wide        the same for wide rows (d > 128), as distance/centre GEMM rounds
  *                         (sklearn KMeans: k-means++ init, Lloyd, best of n_init)
  *   cc_kmeans_f64         the same at float64 for float64 input
+ *   cc_kmeans_f64_cols    cc_kmeans_f64 with every resample on its own columns (feature subsampling)
  *   cc_kmeans_launch_plan which of the three above a fit launches, how often and how large
  *   cc_kmeans_fit         CC.py:282 in one call (makes the calls of cc_kmeans_launch_plan)
  *   cc_euclidean, cc_hc_gather, cc_hc_nnchain_batched, cc_hc_cut
@@ -395,6 +396,21 @@ int cc_kmeans_f64(const double* X, int n, int d, const int32_t* idx_hm, int H, i
                   const double* kpp_u, int kpp_stride, const int32_t* kpp_pos, uint8_t* labels_nh,
                   int ldl, double* inertia, int32_t* n_iter, void* workspace, size_t ws_bytes,
                   int grid, void* stream);
+
+/* cc_kmeans_f64 under feature subsampling: resample h is fitted on its own md columns of X,
+ * ascontiguousarray(X[idx[h]][:, cols[h]]) to sklearn, bit for bit what cc_kmeans_f64 gives on that
+ * materialised matrix.  cols_hmd is a device int32 [H][md] (4-B aligned): row h holds the ascending
+ * columns of resample h, every entry in [0, d) (the caller checks the entries: they are read as
+ * given); 1 <= md <= d, and d stays the row stride of X.  Only the per-resample setup gathers; the
+ * engine runs at row width md, so workspace and launch planning take md where they take d:
+ * cc_kmeans_f64_workspace_bytes(m, md, ...) and cc_kmeans_launch_plan(md, ...).  Every other
+ * argument is cc_kmeans_f64's, which keeps its prototype and passes no column list. */
+int cc_kmeans_f64_cols(const double* X, int n, int d, const int32_t* cols_hmd, int md,
+                       const int32_t* idx_hm, int H, int m, int h_begin, int h_end, const int32_t* Ks,
+                       int nK, int n_init, int max_iter, double tol_rel, const double* kpp_u,
+                       int kpp_stride, const int32_t* kpp_pos, uint8_t* labels_nh, int ldl,
+                       double* inertia, int32_t* n_iter, void* workspace, size_t ws_bytes, int grid,
+                       void* stream);
 
 /* ---- one-call k-means (the advanced entry points above, planned internally) ----------- */
 
