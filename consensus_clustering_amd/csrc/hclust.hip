@@ -6,8 +6,9 @@
 // cuts the tree with _hc_cut.  The distances pdist(X, metric) come from pdist.hip, as one full
 // symmetric float64 [n][n] a fit or one [m][m] a resample; three kernels restate the rest:
 //   gather_kernel   the distances of resample b: D_b[a][c] = Dfull[idx[b][a]][idx[b][c]]
-//   nnchain_batched scipy's nn_chain, one workgroup per tree, with the decisions of predict.hip's
-//                   nnchain_kernel (linkage_shared.hpp); workgroups never communicate
+//   nnchain_batched scipy's nn_chain, one workgroup per tree: the loop of linkage_shared.hpp that
+//                   predict.hip runs too, here in its one-workgroup scope (workgroups never
+//                   communicate)
 //   cut_kernel      the K-cluster cut of every tree and K, straight from nn_chain's raw merges
 //
 // The cut needs no relabelled tree.  nn_chain's merge j joins slots (x_j, y_j), x_j < y_j: slot
@@ -59,112 +60,12 @@ __global__ __launch_bounds__(T) void nnchain_batched_kernel(double* __restrict__
                                                             double* __restrict__ Zall, int* __restrict__ status,
                                                             int* __restrict__ state, int state_in_lds) {
   extern __shared__ unsigned hc_lds[];  // live mask [nw], then (state_in_lds) sizes [m], chain [m]
-  __shared__ double rv[T / 64];
-  __shared__ int ri[T / 64];
-  const int tid = threadIdx.x;
   const size_t b = blockIdx.x, mm = static_cast<size_t>(m);
-  double* D = Dall + b * mm * mm;
-  double* Z = Zall + b * (mm - 1) * 4;
   const int nw = (m + 31) >> 5;
-  unsigned* mask = hc_lds;
   int* size = state_in_lds ? reinterpret_cast<int*>(hc_lds + nw) : state + b * 2 * mm;
-  int* chain = size + m;
-  constexpr double INF = __builtin_huge_val();
-  for (int i = tid; i < m; i += T) size[i] = 1;
-  for (int w = tid; w < nw; w += T) mask[w] = (w < nw - 1 || (m & 31) == 0) ? 0xFFFFFFFFu : ((1u << (m & 31)) - 1u);
-  if (tid == 0) status[b] = HC_OK;
-  __syncthreads();
-  int len = 0;  // uniform: every thread runs the same control flow
-  for (int k = 0; k < m - 1; ++k) {
-    if (len == 0) {  // the first live cluster
-      double v = INF;
-      int i0 = 0x7fffffff;
-      for (int w = tid; w < nw; w += T)
-        if (mask[w]) {
-          i0 = 32 * w + __builtin_ctz(mask[w]);
-          v = 0.0;
-          break;
-        }
-      cc_link::block_argmin<T>(v, i0, rv, ri);
-      if (i0 < 0 || i0 >= m) {  // cannot happen while merges remain; never index with it
-        if (tid == 0) status[b] = HC_NO_NEIGHBOUR;
-        return;
-      }
-      if (tid == 0) chain[0] = i0;
-      __syncthreads();
-      len = 1;
-    }
-    int x, y;
-    double cur;
-    for (;;) {
-      x = chain[len - 1];
-      y = -1;
-      cur = INF;
-      if (len > 1) {
-        y = chain[len - 2];
-        cur = D[x * mm + y];
-      }
-      double v;
-      int bi;
-      cc_link::row_argmin<T, NBH>(D + x * mm, m, x, mask, v, bi);
-      cc_link::block_argmin<T>(v, bi, rv, ri);
-      if (v < cur) {
-        cur = v;
-        y = bi;
-      }
-      // no neighbour: the scan's sentinel (or the -1 of a one-element chain) must never index
-      // anything; the tree is reported and abandoned (every thread holds the same y)
-      if (y < 0 || y >= m) {
-        if (tid == 0) status[b] = HC_NO_NEIGHBOUR;
-        return;
-      }
-      if (len > 1 && y == chain[len - 2]) break;
-      __syncthreads();  // every thread has read chain[len - 2] before it may be overwritten
-      if (tid == 0) chain[len] = y;
-      __syncthreads();
-      ++len;
-    }
-    len -= 2;
-    if (x > y) {
-      const int t = x;
-      x = y;
-      y = t;
-    }
-    const int nx = size[x], ny = size[y];
-    __syncthreads();  // every thread has read the sizes
-    if (tid == 0) {
-      Z[4 * static_cast<size_t>(k) + 0] = x;
-      Z[4 * static_cast<size_t>(k) + 1] = y;
-      Z[4 * static_cast<size_t>(k) + 2] = cur;
-      Z[4 * static_cast<size_t>(k) + 3] = nx + ny;
-      size[x] = 0;
-      size[y] = nx + ny;
-      mask[x >> 5] &= ~(1u << (x & 31));
-    }
-    __syncthreads();
-    const double* rx = D + x * mm;
-    double* ry = D + y * mm;
-    for (int base = 0; base < m; base += T * NBH) {
-      double dx[NBH], dy[NBH];
-#pragma unroll
-      for (int u = 0; u < NBH; ++u) {
-        const int i = base + tid + T * u;
-        dx[u] = i < m ? rx[i] : 0.0;
-        dy[u] = i < m ? ry[i] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < NBH; ++u) {
-        const int i = base + tid + T * u;
-        if (i < m && i != y && cc_link::live(mask, i)) {
-          const int ni = method == CC_LINK_WARD ? size[i] : 0;
-          const double nd = cc_link::lw_update(method, dx[u], dy[u], cur, nx, ny, ni);
-          ry[i] = nd;
-          D[i * mm + y] = nd;
-        }
-      }
-    }
-    __syncthreads();
-  }
+  if (threadIdx.x == 0) status[b] = HC_OK;
+  cc_link::OneGroup<T, NBH> scope{m, status + b, HC_NO_NEIGHBOUR};
+  cc_link::nn_chain(scope, Dall + b * mm * mm, m, method, Zall + b * (mm - 1) * 4, hc_lds, size, size + m);
 }
 
 // ---- cut: one workgroup per (tree b, K index k).  link[] of the m slots in LDS when 4 m bytes

@@ -161,220 +161,69 @@ extern "C" int cc_manhattan(const float* C, int n, int d, double* D, void* strea
 // ---- Agglomerative linkage on the device: scipy.cluster.hierarchy.nn_chain
 // (scipy/cluster/_hierarchy.pyx, the algorithm linkage() runs for 'complete', 'average' and
 // 'weighted'), the tree AgglomerativeClustering cuts (CC.py:306-312 -> sklearn linkage_tree ->
-// hierarchy.linkage).  The same sequence of decisions as scipy's loop: the chain grows from the
-// first live cluster; a step's nearest neighbour of the chain top x is the first index (scan
-// order) of the minimum over live i != x of D[x, i], taken only when strictly below D[x, prev]
-// (so the previous chain element wins ties); mutual neighbours merge (x < y kept as in
-// fastcluster), the merged cluster takes y's row and column, x dies; the Lance-Williams update is
-// the float64 expression of _hierarchy_distance_update.pxi with no contraction.  One workgroup
-// runs the whole chain (every step is a scan or an update over n entries; the full symmetric
-// n x n float64 matrix stays in HBM: 20 GB at n = 50k).  Z is written in merge order, unsorted;
-// the host sorts it by distance (stable) and relabels, as linkage() does after nn_chain.
+// hierarchy.linkage).  The loop itself, with scipy's sequence of decisions, is cc_link::nn_chain
+// (linkage_shared.hpp); the kernels here only give it a scope.  Every step is a scan or an
+// update over n entries; the full symmetric n x n float64 matrix stays in HBM (20 GB at
+// n = 50k).  Z is written in merge order, unsorted; the host sorts it by distance (stable) and
+// relabels, as linkage() does after nn_chain.
 //
-// Round 4: the live set is a bitmask in LDS (n / 8 bytes), and every row pass issues its loads
-// in batches of NB per thread before any compare (branch-free: dead and diagonal entries read
-// as +inf), so a scan is a few HBM round trips instead of one per element and thread (8.3 s ->
-// see DESIGN.md K7 at n = 50k).
+// The live set is a bitmask in LDS (n / 8 bytes), and every row pass issues its loads in batches
+// of NB per thread before any compare (branch-free: dead and diagonal entries read as +inf), so
+// a scan is a few HBM round trips instead of one per element and thread.
 //
 // Single linkage: sklearn's own path (linkage_tree -> _hierarchical_fast.mst_linkage_core, Prim's
-// MST-LINKAGE-CORE, for a non-precomputed metric such as the reference's 'manhattan'): from node 0,
-// each step folds the current node's row into the running minimum distance of every node not in
-// the tree (strict <) and takes the first node of the smallest, as mst_kernel does with D's rows
-// (the cityblock values of DistanceMetric64 are cc_manhattan's, same terms and order).
+// MST-LINKAGE-CORE, for a non-precomputed metric such as the reference's 'manhattan'), which is
+// cc_link::prim over D's rows (the cityblock values of DistanceMetric64 are cc_manhattan's, same
+// terms and order).
 namespace {
 
-constexpr int LT = 1024;  // threads of the linkage workgroup
+constexpr int LT = 1024;  // threads of the one workgroup of a G = 0 run
 constexpr int NB = 8;     // loads per thread in flight per row pass
 
-using cc_link::live;
-using cc_link::lw_update;  // linkage_shared.hpp: shared with the batched trees of hclust.hip
+// error word of the workspace header (bits, so that neither report hides the other)
+constexpr unsigned LINK_ERR_BARRIER = 1u;       // a grid barrier timed out
+constexpr unsigned LINK_ERR_NO_NEIGHBOUR = 2u;  // an nn_chain scan found no live finite neighbour
 
-__device__ __forceinline__ void block_argmin(double& v, int& i, double* rv, int* ri) {
-  cc_link::block_argmin<LT>(v, i, rv, ri);
-}
-
-__device__ __forceinline__ void row_argmin(const double* row, int n, int x, const unsigned* mask, double& v,
-                                           int& bi) {
-  cc_link::row_argmin<LT, NB>(row, n, x, mask, v, bi);
-}
-
-__global__ __launch_bounds__(LT) void nnchain_kernel(double* __restrict__ D, int n, int method,
-                                                     double* __restrict__ Z, int* __restrict__ size,
-                                                     int* __restrict__ chain) {
+// One workgroup, one tree: size and chain in the workspace, the live / in-tree bits in LDS.
+__global__ __launch_bounds__(LT) void nnchain_group_kernel(double* __restrict__ D, int n, int method,
+                                                           double* __restrict__ Z, int* __restrict__ size,
+                                                           int* __restrict__ chain, int* __restrict__ err) {
   extern __shared__ unsigned mask[];  // live clusters, one bit each
-  __shared__ double rv[LT / 64];
-  __shared__ int ri[LT / 64];
-  const int tid = threadIdx.x;
-  const size_t nn = static_cast<size_t>(n);
-  const int nw = (n + 31) >> 5;
-  constexpr double INF = __builtin_huge_val();
-  for (int i = tid; i < n; i += LT) size[i] = 1;
-  for (int w = tid; w < nw; w += LT) mask[w] = (w < nw - 1 || (n & 31) == 0) ? 0xFFFFFFFFu : ((1u << (n & 31)) - 1u);
-  __syncthreads();
-  int len = 0;  // uniform: every thread runs the same control flow
-  for (int k = 0; k < n - 1; ++k) {
-    if (len == 0) {  // the first live cluster
-      double v = INF;
-      int i0 = 0x7fffffff;
-      for (int w = tid; w < nw; w += LT)
-        if (mask[w]) {
-          i0 = 32 * w + __builtin_ctz(mask[w]);
-          v = 0.0;
-          break;
-        }
-      block_argmin(v, i0, rv, ri);
-      if (tid == 0) chain[0] = i0;
-      __syncthreads();
-      len = 1;
-    }
-    int x, y;
-    double cur;
-    for (;;) {
-      x = chain[len - 1];
-      y = -1;
-      cur = INF;
-      if (len > 1) {
-        y = chain[len - 2];
-        cur = D[x * nn + y];
-      }
-      double v;
-      int bi;
-      row_argmin(D + x * nn, n, x, mask, v, bi);
-      block_argmin(v, bi, rv, ri);
-      if (v < cur) {
-        cur = v;
-        y = bi;
-      }
-      if (len > 1 && y == chain[len - 2]) break;
-      __syncthreads();  // every thread has read chain[len - 2] before it may be overwritten
-      if (tid == 0) chain[len] = y;
-      __syncthreads();
-      ++len;
-    }
-    len -= 2;
-    if (x > y) {
-      const int t = x;
-      x = y;
-      y = t;
-    }
-    const int nx = size[x], ny = size[y];
-    __syncthreads();  // every thread has read the sizes
-    if (tid == 0) {
-      Z[4 * static_cast<size_t>(k) + 0] = x;
-      Z[4 * static_cast<size_t>(k) + 1] = y;
-      Z[4 * static_cast<size_t>(k) + 2] = cur;
-      Z[4 * static_cast<size_t>(k) + 3] = nx + ny;
-      size[x] = 0;
-      size[y] = nx + ny;
-      mask[x >> 5] &= ~(1u << (x & 31));
-    }
-    __syncthreads();
-    const double* rx = D + x * nn;
-    double* ry = D + y * nn;
-    for (int base = 0; base < n; base += LT * NB) {
-      double dx[NB], dy[NB];
-#pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        const int i = base + tid + LT * u;
-        dx[u] = i < n ? rx[i] : 0.0;
-        dy[u] = i < n ? ry[i] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        const int i = base + tid + LT * u;
-        if (i < n && i != y && live(mask, i)) {
-          const int ni = method == CC_LINK_WARD ? size[i] : 0;
-          const double nd = lw_update(method, dx[u], dy[u], cur, nx, ny, ni);
-          ry[i] = nd;
-          D[i * nn + y] = nd;
-        }
-      }
-    }
-    __syncthreads();
-  }
+  cc_link::OneGroup<LT, NB> scope{n, err, static_cast<int>(LINK_ERR_NO_NEIGHBOUR)};
+  cc_link::nn_chain(scope, D, n, method, Z, mask, size, chain);
 }
 
-// sklearn mst_linkage_core (Prim) over the rows of the symmetric D: out [n-1][3] = (current
-// node, new node, distance) per step; cur: the running minimum distance of every node ([n]
-// float64 workspace).
-__global__ __launch_bounds__(LT) void mst_kernel(const double* __restrict__ D, int n, double* __restrict__ out,
-                                                 double* __restrict__ cur) {
+__global__ __launch_bounds__(LT) void mst_group_kernel(const double* __restrict__ D, int n, double* __restrict__ out,
+                                                       double* __restrict__ cur) {
   extern __shared__ unsigned tree[];  // in_tree, one bit per node
-  __shared__ double rv[LT / 64];
-  __shared__ int ri[LT / 64];
-  const int tid = threadIdx.x;
-  const int nw = (n + 31) >> 5;
-  constexpr double INF = __builtin_huge_val();
-  for (int i = tid; i < n; i += LT) cur[i] = INF;
-  for (int w = tid; w < nw; w += LT) tree[w] = 0u;
-  __syncthreads();
-  int node = 0;
-  for (int k = 0; k < n - 1; ++k) {
-    if (tid == 0) tree[node >> 5] |= 1u << (node & 31);
-    __syncthreads();
-    const double* row = D + static_cast<size_t>(node) * n;
-    double v = INF;
-    int bi = 0x7fffffff;
-    for (int base = 0; base < n; base += LT * NB) {
-      double l[NB], r[NB];
-#pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        const int j = base + tid + LT * u;
-        l[u] = j < n ? row[j] : INF;
-        r[u] = j < n ? cur[j] : INF;
-      }
-#pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        const int j = base + tid + LT * u;
-        if (j < n && !((tree[j >> 5] >> (j & 31)) & 1u)) {
-          double c = r[u];
-          if (l[u] < c) {  // left_value < right_value
-            c = l[u];
-            cur[j] = c;
-          }
-          if (c < v) {  // current_distances[j] < new_distance: the first minimum
-            v = c;
-            bi = j;
-          }
-        }
-      }
-    }
-    block_argmin(v, bi, rv, ri);
-    const int nxt = (v < INF) ? bi : 0;  // sklearn's new_node starts at 0
-    if (tid == 0) {
-      out[3 * static_cast<size_t>(k) + 0] = node;
-      out[3 * static_cast<size_t>(k) + 1] = nxt;
-      out[3 * static_cast<size_t>(k) + 2] = v;
-    }
-    node = nxt;
-    __syncthreads();  // cur[] of this step is written before the next step reads it
-  }
+  cc_link::OneGroup<LT, NB> scope{n, nullptr, 0};
+  cc_link::prim(scope, D, n, out, cur, tree);
 }
 
-// ---- Grid forms (round 4): the same decisions on G co-resident workgroups.  Workgroup g owns
-// the index slice [n g / G, n (g + 1) / G): it scans its slice of a row, updates its slice of a
-// merged row and its slice's entries of the merged column, and keeps the running minima of its
-// slice (Prim).  Each workgroup keeps a replica of the whole live / in-tree bitmask in LDS and
-// private copies of the chain and the cluster sizes, and every workgroup takes every decision
-// itself from the same data, so the control flow is identical on all of them.  Per step the
-// slices' (minimum, first index) pairs go through a grid barrier and every workgroup reduces
-// them in slice order (strict <: the lowest index wins ties, as the one-workgroup scan does).
-// nn_chain needs a second barrier after each Lance-Williams update (a later scan of another
-// slice reads the merged column).  The barrier is a counter and a generation word in the
-// workspace, with agent-scope release / acquire fences (buffer_wbl2 / buffer_inv on gfx950, so
-// the D writes of one XCD are seen by the others); a workgroup that waits for more than ~2^27
-// polls sets an error word and every workgroup leaves (cc_linkage_check reports it).  The
-// workgroups are made co-resident, not assumed so: G is capped by the occupancy query of the
-// kernel at its dynamic LDS, and the grid forms are started with hipLaunchCooperativeKernel,
-// which the runtime starts only when all G workgroups can run at once; if it refuses, the
-// one-workgroup kernel runs instead (nothing has been written by then).
+// ---- Grid forms: the same loops on G co-resident workgroups.  Workgroup g owns the index slice
+// [n g / G, n (g + 1) / G): it scans its slice of a row, updates its slice of a merged row and
+// its slice's entries of the merged column, and keeps the running minima of its slice (Prim).
+// Each workgroup keeps a replica of the whole live / in-tree bitmask in LDS and private copies of
+// the chain and the cluster sizes, and every workgroup takes every decision itself from the same
+// data, so the control flow is identical on all of them.  Per step the slices' (minimum, first
+// index) pairs go through a grid barrier and every workgroup reduces them in slice order (strict
+// <: the lowest index wins ties, as the scan of one workgroup does).  nn_chain needs a second
+// barrier after each Lance-Williams update (a later scan of another slice reads the merged
+// column).  The barrier is a counter and a generation word in the workspace, with agent-scope
+// release / acquire fences (buffer_wbl2 / buffer_inv on gfx950, so the D writes of one XCD are
+// seen by the others); a workgroup that waits for more than ~2^27 polls sets an error bit and
+// every workgroup leaves (cc_linkage_check reports it).  The workgroups are made co-resident,
+// not assumed so: G is capped by the occupancy query of the kernel at its dynamic LDS, and the
+// grid forms are started with hipLaunchCooperativeKernel, which the runtime starts only when all
+// G workgroups can run at once; if it refuses, the one-workgroup form runs instead (nothing has
+// been written by then).
 constexpr int LG = 256;    // threads of a grid-form workgroup
 constexpr int GMAX = 128;  // workgroups of a grid form (all co-resident: one per CU at most)
 constexpr int NBG = 8;     // loads per thread in flight per slice pass
 constexpr size_t GHDR = 256;  // workspace header: barrier count, generation, error
 
 struct GridWs {
-  unsigned* bar;    // [0] arrivals, [1] generation, [2] error
+  unsigned* bar;    // [0] arrivals, [1] generation, [2] error (LINK_ERR_* bits)
   double* pv;       // [2][GMAX] slice minima (double-buffered by barrier parity)
   int* pi;          // [2][GMAX] their indices
 };
@@ -418,8 +267,10 @@ __device__ bool grid_sync(const GridWs& gw, unsigned& gen) {
       while (__hip_atomic_load(&gw.bar[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != want) {
         __builtin_amdgcn_s_sleep(2);
         if ((++polls & 1023u) == 0) {
+          // an error of another workgroup (it has left), or this wait has lasted too long; the
+          // bit is or-ed in, so a no-neighbour report that a late waiter meets here is kept
           if (__hip_atomic_load(&gw.bar[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || polls > (1u << 27)) {
-            __hip_atomic_store(&gw.bar[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_or(&gw.bar[2], LINK_ERR_BARRIER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             ok = 0;
             break;
           }
@@ -434,33 +285,6 @@ __device__ bool grid_sync(const GridWs& gw, unsigned& gen) {
   __syncthreads();
   ++gen;
   return s_ok != 0;
-}
-
-// Block minimum of (v, i) over LG threads: the lower value, ties to the lower index.
-__device__ __forceinline__ void block_argmin_g(double& v, int& i, double* rv, int* ri) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(v, o);
-    const int oi = __shfl_xor(i, o);
-    if (ov < v || (ov == v && oi < i)) {
-      v = ov;
-      i = oi;
-    }
-  }
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-    rv[w] = v;
-    ri[w] = i;
-  }
-  __syncthreads();
-  v = rv[0];
-  i = ri[0];
-  for (int k = 1; k < LG / 64; ++k)
-    if (rv[k] < v || (rv[k] == v && ri[k] < i)) {
-      v = rv[k];
-      i = ri[k];
-    }
-  __syncthreads();  // rv / ri may be rewritten by the next call
 }
 
 // Publish this workgroup's slice minimum, pass the barrier, and reduce every slice's in slice
@@ -483,190 +307,45 @@ __device__ bool grid_argmin(const GridWs& gw, unsigned& gen, double& v, int& i, 
         __HIP_MEMORY_SCOPE_AGENT)));
     i = __hip_atomic_load(gw.pi + par * GMAX + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  block_argmin_g(v, i, rv, ri);
+  cc_link::block_argmin<LG>(v, i, rv, ri);
   return true;
 }
+
+// The scope of workgroup blockIdx.x of gridDim.x over one tree (linkage_shared.hpp).
+struct GridScope {
+  static constexpr int T = LG, NB = NBG;
+  GridWs gw;
+  unsigned gen = 0;
+  int j0, j1;
+  __device__ GridScope(void* ws, int n)
+      : gw(grid_ws(ws)),
+        j0(static_cast<int>(static_cast<int64_t>(n) * blockIdx.x / gridDim.x)),
+        j1(static_cast<int>(static_cast<int64_t>(n) * (blockIdx.x + 1) / gridDim.x)) {}
+  __device__ bool tree_argmin(double& v, int& i, double* rv, int* ri) { return grid_argmin(gw, gen, v, i, rv, ri); }
+  __device__ bool after_update() { return grid_sync<true>(gw, gen); }
+  __device__ bool writes_out() const { return blockIdx.x == 0; }
+  // every workgroup takes this decision from the same reduced values and leaves; one reports it
+  __device__ void no_neighbour() {
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+      __hip_atomic_fetch_or(&gw.bar[2], LINK_ERR_NO_NEIGHBOUR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
 
 __global__ __launch_bounds__(LG) void nnchain_grid_kernel(double* __restrict__ D, int n, int method,
                                                           double* __restrict__ Z, int* __restrict__ sizes,
                                                           int* __restrict__ chains, void* ws) {
   extern __shared__ unsigned mask[];  // live clusters, one bit each (a replica per workgroup)
-  __shared__ double rv[LG / 64];
-  __shared__ int ri[LG / 64];
-  __shared__ int s_i0;
-  const GridWs gw = grid_ws(ws);
-  const int tid = threadIdx.x, G = gridDim.x, g = blockIdx.x;
-  const int j0 = static_cast<int>(static_cast<int64_t>(n) * g / G);
-  const int j1 = static_cast<int>(static_cast<int64_t>(n) * (g + 1) / G);
-  const size_t nn = static_cast<size_t>(n);
-  int* size = sizes + static_cast<size_t>(g) * nn;   // private copies: no sharing
-  int* chain = chains + static_cast<size_t>(g) * nn;
-  const int nw = (n + 31) >> 5;
-  constexpr double INF = __builtin_huge_val();
-  for (int i = tid; i < n; i += LG) size[i] = 1;
-  for (int w = tid; w < nw; w += LG) mask[w] = (w < nw - 1 || (n & 31) == 0) ? 0xFFFFFFFFu : ((1u << (n & 31)) - 1u);
-  __syncthreads();
-  unsigned gen = 0;
-  int len = 0;
-  for (int k = 0; k < n - 1; ++k) {
-    if (len == 0) {  // the first live cluster (from the replicated mask)
-      double v = INF;
-      int i0 = 0x7fffffff;
-      for (int w = tid; w < nw; w += LG)
-        if (mask[w]) {
-          i0 = 32 * w + __builtin_ctz(mask[w]);
-          v = 0.0;
-          break;
-        }
-      block_argmin_g(v, i0, rv, ri);
-      if (tid == 0) s_i0 = i0;
-      __syncthreads();
-      if (tid == 0) chain[0] = s_i0;
-      len = 1;
-    }
-    int x, y;
-    double cur;
-    for (;;) {
-      __syncthreads();  // chain[] writes of thread 0 are visible to the workgroup
-      x = chain[len - 1];
-      y = -1;
-      cur = INF;
-      if (len > 1) {
-        y = chain[len - 2];
-        cur = D[x * nn + y];
-      }
-      double v = INF;
-      int bi = 0x7fffffff;
-      const double* row = D + x * nn;
-      for (int base = j0; base < j1; base += LG * NBG) {
-        double d[NBG];
-#pragma unroll
-        for (int u = 0; u < NBG; ++u) {
-          const int i = base + tid + LG * u;
-          d[u] = i < j1 ? row[i] : INF;
-        }
-#pragma unroll
-        for (int u = 0; u < NBG; ++u) {
-          const int i = base + tid + LG * u;
-          if (i < j1 && i != x && live(mask, i) && d[u] < v) {
-            v = d[u];
-            bi = i;
-          }
-        }
-      }
-      block_argmin_g(v, bi, rv, ri);
-      if (!grid_argmin(gw, gen, v, bi, rv, ri)) return;
-      if (v < cur) {
-        cur = v;
-        y = bi;
-      }
-      if (len > 1 && y == chain[len - 2]) break;
-      __syncthreads();  // every thread has read chain[len - 2]
-      if (tid == 0) chain[len] = y;
-      ++len;
-    }
-    len -= 2;
-    if (x > y) {
-      const int t = x;
-      x = y;
-      y = t;
-    }
-    const int nx = size[x], ny = size[y];
-    __syncthreads();  // every thread has read the sizes
-    if (tid == 0) {
-      if (g == 0) {
-        Z[4 * static_cast<size_t>(k) + 0] = x;
-        Z[4 * static_cast<size_t>(k) + 1] = y;
-        Z[4 * static_cast<size_t>(k) + 2] = cur;
-        Z[4 * static_cast<size_t>(k) + 3] = nx + ny;
-      }
-      size[x] = 0;
-      size[y] = nx + ny;
-      mask[x >> 5] &= ~(1u << (x & 31));
-    }
-    __syncthreads();
-    const double* rx = D + x * nn;
-    double* ry = D + y * nn;
-    for (int base = j0; base < j1; base += LG * NBG) {
-      double dx[NBG], dy[NBG];
-#pragma unroll
-      for (int u = 0; u < NBG; ++u) {
-        const int i = base + tid + LG * u;
-        dx[u] = i < j1 ? rx[i] : 0.0;
-        dy[u] = i < j1 ? ry[i] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < NBG; ++u) {
-        const int i = base + tid + LG * u;
-        if (i < j1 && i != y && live(mask, i)) {
-          const int ni = method == CC_LINK_WARD ? size[i] : 0;
-          const double nd = lw_update(method, dx[u], dy[u], cur, nx, ny, ni);
-          ry[i] = nd;
-          D[i * nn + y] = nd;
-        }
-      }
-    }
-    if (!grid_sync<true>(gw, gen)) return;  // the merged row and column before any later scan
-  }
+  GridScope scope(ws, n);
+  const size_t own = static_cast<size_t>(blockIdx.x) * static_cast<size_t>(n);  // private copies: no sharing
+  cc_link::nn_chain(scope, D, n, method, Z, mask, sizes + own, chains + own);
 }
 
-// sklearn mst_linkage_core on G workgroups: each keeps the running minima of its slice.
+// each workgroup keeps the running minima of its slice
 __global__ __launch_bounds__(LG) void mst_grid_kernel(const double* __restrict__ D, int n, double* __restrict__ out,
                                                       double* __restrict__ cur, void* ws) {
   extern __shared__ unsigned tree[];  // in_tree, one bit per node (a replica per workgroup)
-  __shared__ double rv[LG / 64];
-  __shared__ int ri[LG / 64];
-  const GridWs gw = grid_ws(ws);
-  const int tid = threadIdx.x, G = gridDim.x, g = blockIdx.x;
-  const int j0 = static_cast<int>(static_cast<int64_t>(n) * g / G);
-  const int j1 = static_cast<int>(static_cast<int64_t>(n) * (g + 1) / G);
-  const int nw = (n + 31) >> 5;
-  constexpr double INF = __builtin_huge_val();
-  for (int i = j0 + tid; i < j1; i += LG) cur[i] = INF;
-  for (int w = tid; w < nw; w += LG) tree[w] = 0u;
-  __syncthreads();
-  unsigned gen = 0;
-  int node = 0;
-  for (int k = 0; k < n - 1; ++k) {
-    if (tid == 0) tree[node >> 5] |= 1u << (node & 31);
-    __syncthreads();
-    const double* row = D + static_cast<size_t>(node) * n;
-    double v = INF;
-    int bi = 0x7fffffff;
-    for (int base = j0; base < j1; base += LG * NBG) {
-      double l[NBG], r[NBG];
-#pragma unroll
-      for (int u = 0; u < NBG; ++u) {
-        const int j = base + tid + LG * u;
-        l[u] = j < j1 ? row[j] : INF;
-        r[u] = j < j1 ? cur[j] : INF;
-      }
-#pragma unroll
-      for (int u = 0; u < NBG; ++u) {
-        const int j = base + tid + LG * u;
-        if (j < j1 && !((tree[j >> 5] >> (j & 31)) & 1u)) {
-          double c = r[u];
-          if (l[u] < c) {  // left_value < right_value
-            c = l[u];
-            cur[j] = c;
-          }
-          if (c < v) {  // the first minimum
-            v = c;
-            bi = j;
-          }
-        }
-      }
-    }
-    block_argmin_g(v, bi, rv, ri);
-    if (!grid_argmin(gw, gen, v, bi, rv, ri)) return;
-    const int nxt = (v < INF) ? bi : 0;  // sklearn's new_node starts at 0
-    if (g == 0 && tid == 0) {
-      out[3 * static_cast<size_t>(k) + 0] = node;
-      out[3 * static_cast<size_t>(k) + 1] = nxt;
-      out[3 * static_cast<size_t>(k) + 2] = v;
-    }
-    node = nxt;
-  }
+  GridScope scope(ws, n);
+  cc_link::prim(scope, D, n, out, cur, tree);
 }
 
 size_t mask_bytes(int n) { return static_cast<size_t>((n + 31) >> 5) * sizeof(unsigned); }
@@ -674,9 +353,9 @@ size_t mask_bytes(int n) { return static_cast<size_t>((n + 31) >> 5) * sizeof(un
 // the dynamic LDS of the bitmask (up to the 160 KiB of a CU, less the static part)
 constexpr size_t MASK_LDS_MAX = 160 * 1024 - 1024;
 
-// Workgroups of the grid forms for n (CCMI_LINK_G overrides; 0 = the one-workgroup kernels):
-// about 1536 entries per slice (six loads per thread), at most GMAX and at most what the kernel's
-// occupancy at its dynamic LDS keeps resident on all CUs at once.
+// Workgroups of the grid forms for n (CCMI_LINK_G overrides; 0 = one workgroup): about 1536
+// entries per slice (six loads per thread), at most GMAX and at most what the kernel's occupancy
+// at its dynamic LDS keeps resident on all CUs at once.
 template <typename Kern>
 int link_groups(int n, Kern kernel) {
   const char* e = std::getenv("CCMI_LINK_G");
@@ -715,13 +394,43 @@ hipError_t launch_grid(void (*kernel)(KArgs...), int G, size_t lds, hipStream_t 
   return hipGetLastError();
 }
 
-// Both forms: the barrier header (zeroed at every launch, so cc_linkage_check also reads a
-// one-workgroup run's as clean), then the sizes and chains ([G][n] each, or [n] at G = 0) or the
+// Both forms: the barrier header (zeroed at every launch, so cc_linkage_check never reads the
+// error word of an earlier call), then the sizes and chains ([G][n] each, or [n] at G = 0) or the
 // running minima.
 size_t nnchain_ws(int n, int G) {
   return grid_ws_bytes() + 2 * static_cast<size_t>(G > 0 ? G : 1) * static_cast<size_t>(n) * sizeof(int);
 }
 size_t mst_ws(int n, int) { return grid_ws_bytes() + static_cast<size_t>(n) * sizeof(double); }
+
+// What cc_linkage_nnchain and cc_linkage_mst do around their kernels: refuse bad arguments, zero
+// the header, try the cooperative grid launch (G > 0), fall back to one workgroup, report.
+// grid() returns the launch's error; one() launches.
+template <typename Grid, typename One>
+int run_linkage(const char* what, bool args_ok, void* workspace, int G, hipStream_t st, Grid grid, One one) {
+  if (!args_ok) {
+    cc::set_error(std::string(what) + ": bad arguments");
+    return CC_ERR_ARG;
+  }
+  hipError_t e = hipMemsetAsync(workspace, 0, GHDR, st);
+  if (e != hipSuccess) {
+    cc::set_error(std::string(what) + ": " + hipGetErrorString(e));
+    return CC_ERR_HIP;
+  }
+  e = hipErrorNotReady;
+  if (G > 0) {
+    e = grid();
+    if (e != hipSuccess) (void)hipGetLastError();  // refused before any workgroup ran
+  }
+  if (e != hipSuccess) {
+    one();
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) {
+    cc::set_error(std::string(what) + ": " + hipGetErrorString(e));
+    return CC_ERR_HIP;
+  }
+  return CC_OK;
+}
 
 }  // namespace
 
@@ -732,66 +441,44 @@ extern "C" size_t cc_linkage_workspace_bytes(int n) {
 extern "C" int cc_linkage_nnchain(double* D, int n, int method, double* Z, void* workspace, size_t ws_bytes,
                                   void* stream) {
   const int G = n > 0 ? link_groups(n, nnchain_grid_kernel) : 0;
-  if (!D || !Z || n < 2 || !workspace || ws_bytes < nnchain_ws(n, G) ||
-      (method != CC_LINK_AVERAGE && method != CC_LINK_COMPLETE && method != CC_LINK_WEIGHTED &&
-       method != CC_LINK_WARD) ||
-      mask_bytes(n) > MASK_LDS_MAX) {
-    cc::set_error("cc_linkage_nnchain: bad arguments");
-    return CC_ERR_ARG;
-  }
+  const bool args_ok = D && Z && n >= 2 && workspace && ws_bytes >= nnchain_ws(n, G) &&
+                       (method == CC_LINK_AVERAGE || method == CC_LINK_COMPLETE || method == CC_LINK_WEIGHTED ||
+                        method == CC_LINK_WARD) &&
+                       mask_bytes(n) <= MASK_LDS_MAX;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e = hipMemsetAsync(workspace, 0, GHDR, st);
-  if (e != hipSuccess) {
-    cc::set_error(std::string("cc_linkage_nnchain: ") + hipGetErrorString(e));
-    return CC_ERR_HIP;
-  }
-  int* sizes = reinterpret_cast<int*>(static_cast<char*>(workspace) + grid_ws_bytes());
-  e = hipErrorNotReady;
-  if (G > 0) {
-    e = launch_grid(nnchain_grid_kernel, G, mask_bytes(n), st, D, n, method, Z, sizes,
-                    sizes + static_cast<size_t>(G) * n, workspace);
-    if (e != hipSuccess) (void)hipGetLastError();  // refused before any workgroup ran
-  }
-  if (e != hipSuccess) {
-    hipLaunchKernelGGL(nnchain_kernel, dim3(1), dim3(LT), mask_bytes(n), st, D, n, method, Z, sizes, sizes + n);
-    e = hipGetLastError();
-  }
-  if (e != hipSuccess) {
-    cc::set_error(std::string("cc_linkage_nnchain: ") + hipGetErrorString(e));
-    return CC_ERR_HIP;
-  }
-  return CC_OK;
+  char* const ws = static_cast<char*>(workspace);
+  return run_linkage(
+      "cc_linkage_nnchain", args_ok, workspace, G, st,
+      [&] {
+        int* sizes = reinterpret_cast<int*>(ws + grid_ws_bytes());
+        return launch_grid(nnchain_grid_kernel, G, mask_bytes(n), st, D, n, method, Z, sizes,
+                           sizes + static_cast<size_t>(G) * n, workspace);
+      },
+      [&] {
+        int* sizes = reinterpret_cast<int*>(ws + grid_ws_bytes());
+        int* err = reinterpret_cast<int*>(ws) + 2;  // GridWs::bar[2]
+        hipLaunchKernelGGL(nnchain_group_kernel, dim3(1), dim3(LT), mask_bytes(n), st, D, n, method, Z, sizes,
+                           sizes + n, err);
+      });
 }
 
 extern "C" size_t cc_linkage_mst_workspace_bytes(int n) { return n > 0 ? mst_ws(n, link_groups(n, mst_grid_kernel)) : 0; }
 
 extern "C" int cc_linkage_mst(const double* D, int n, double* out, void* workspace, size_t ws_bytes, void* stream) {
   const int G = n > 0 ? link_groups(n, mst_grid_kernel) : 0;
-  if (!D || !out || n < 2 || !workspace || ws_bytes < mst_ws(n, G) || mask_bytes(n) > MASK_LDS_MAX) {
-    cc::set_error("cc_linkage_mst: bad arguments");
-    return CC_ERR_ARG;
-  }
+  const bool args_ok = D && out && n >= 2 && workspace && ws_bytes >= mst_ws(n, G) && mask_bytes(n) <= MASK_LDS_MAX;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e = hipMemsetAsync(workspace, 0, GHDR, st);
-  if (e != hipSuccess) {
-    cc::set_error(std::string("cc_linkage_mst: ") + hipGetErrorString(e));
-    return CC_ERR_HIP;
-  }
-  double* cur = reinterpret_cast<double*>(static_cast<char*>(workspace) + grid_ws_bytes());
-  e = hipErrorNotReady;
-  if (G > 0) {
-    e = launch_grid(mst_grid_kernel, G, mask_bytes(n), st, D, n, out, cur, workspace);
-    if (e != hipSuccess) (void)hipGetLastError();  // refused before any workgroup ran
-  }
-  if (e != hipSuccess) {
-    hipLaunchKernelGGL(mst_kernel, dim3(1), dim3(LT), mask_bytes(n), st, D, n, out, cur);
-    e = hipGetLastError();
-  }
-  if (e != hipSuccess) {
-    cc::set_error(std::string("cc_linkage_mst: ") + hipGetErrorString(e));
-    return CC_ERR_HIP;
-  }
-  return CC_OK;
+  char* const ws = static_cast<char*>(workspace);
+  return run_linkage(
+      "cc_linkage_mst", args_ok, workspace, G, st,
+      [&] {
+        return launch_grid(mst_grid_kernel, G, mask_bytes(n), st, D, n, out,
+                           reinterpret_cast<double*>(ws + grid_ws_bytes()), workspace);
+      },
+      [&] {
+        hipLaunchKernelGGL(mst_group_kernel, dim3(1), dim3(LT), mask_bytes(n), st, D, n, out,
+                           reinterpret_cast<double*>(ws + grid_ws_bytes()));
+      });
 }
 
 extern "C" int cc_linkage_check(const void* workspace, size_t ws_bytes, void* stream) {
@@ -804,6 +491,10 @@ extern "C" int cc_linkage_check(const void* workspace, size_t ws_bytes, void* st
   if (e == hipSuccess) e = hipMemcpy(&err, static_cast<const char*>(workspace) + 2 * sizeof(unsigned), sizeof(err), hipMemcpyDeviceToHost);
   if (e != hipSuccess) {
     cc::set_error(std::string("cc_linkage_check: ") + hipGetErrorString(e));
+    return CC_ERR_HIP;
+  }
+  if (err & LINK_ERR_NO_NEIGHBOUR) {
+    cc::set_error("cc_linkage_nnchain: the tree found no neighbour (non-finite distances?); its merges are invalid");
     return CC_ERR_HIP;
   }
   if (err) {

@@ -191,7 +191,9 @@ int cc_manhattan(const float* C, int n, int d, double* D, void* stream);
  * (x, y, distance, size) per merge in nn_chain's merge order, before linkage()'s stable sort by
  * distance and relabelling (done by the caller).  Runs on G co-resident workgroups joined by
  * grid barriers (G from n; CCMI_LINK_G overrides, 0 = one workgroup); workspace of
- * cc_linkage_workspace_bytes(n) bytes; call cc_linkage_check after it. */
+ * cc_linkage_workspace_bytes(n) bytes; call cc_linkage_check after it.  A scan that finds no
+ * live finite neighbour (non-finite distances) indexes nothing: the tree is abandoned, Z is
+ * invalid and cc_linkage_check reports it. */
 #define CC_LINK_AVERAGE 0
 #define CC_LINK_COMPLETE 1
 #define CC_LINK_WEIGHTED 2
@@ -214,8 +216,9 @@ size_t cc_linkage_mst_workspace_bytes(int n);
 int cc_linkage_mst(const double* D, int n, double* out, void* workspace, size_t ws_bytes, void* stream);
 
 /* After cc_linkage_nnchain / cc_linkage_mst on `stream` with this workspace: synchronises the
- * stream and returns CC_ERR_HIP if a grid barrier of the linkage timed out (its output is then
- * invalid), else CC_OK. */
+ * stream and returns CC_ERR_HIP if cc_linkage_nnchain found no neighbour (message "... found no
+ * neighbour ...") or a grid barrier of the linkage timed out (the output is then invalid), else
+ * CC_OK. */
 int cc_linkage_check(const void* workspace, size_t ws_bytes, void* stream);
 
 /* Hierarchical base clusterer (CC.py:282 with AgglomerativeClustering(linkage = ward | average |

@@ -115,7 +115,9 @@ def test_batched_nn_chain_with_ties(link):
 
 @pytest.mark.parametrize("m,link", [(6050, "complete"), (8195, "ward"), (8195, "average"), (8195, "complete")])
 def test_batched_nn_chain_large_trees_equal_scipy(m, link):
-    """The two branches of nnchain_batched_kernel that only a large tree takes (hclust.hip).
+    """The two paths of the batched nn_chain that only a large tree takes: where hclust.hip's
+    nnchain_batched_kernel puts the chain state, and the second row pass of the shared loop
+    (cc_link::nn_chain, linkage_shared.hpp).
 
     Chain state in the workspace: state_in_lds(m) asks 4 ceil(m / 32) bytes of live mask plus 8 m
     bytes of sizes and chain to fit HC_LDS_STATE_MAX = 49152.  m = 6049 has 190 mask words,
@@ -141,7 +143,7 @@ def test_batched_nn_chain_large_trees_equal_scipy(m, link):
 def test_check_reads_every_status_word():
     """cc_hc_check over more trees than one of its 1024-word chunks: 1030 trees of three leaves.
     All finite: the trees on both sides of the chunk edge equal scipy.  A tree whose distances
-    are all +inf finds no neighbour (the kernel's defined error return: the scan's sentinel is
+    are all +inf finds no neighbour (the loop's defined error return in every form: the scan's sentinel is
     refused before anything is indexed), and the call raises naming the first such tree, also
     when that tree's status word lies in the second chunk."""
     rs = np.random.RandomState(7)

@@ -97,7 +97,7 @@ def test_device_mst_equals_oracle(n, seed, ties):
 @pytest.mark.parametrize("n,seed,ties", [(3, 0, True), (257, 1, True), (1500, 2, False), (2000, 3, True)])
 def test_grid_linkage_equals_oracle(G, n, seed, ties, monkeypatch):
     """The grid forms (G workgroups over index slices, grid barriers; CCMI_LINK_G = 0 is the
-    one-workgroup kernel) give the oracle's nn_chain merges and Prim edges bit for bit, ties
+    same loop in one workgroup of 1024 threads) give the oracle's nn_chain merges and Prim edges bit for bit, ties
     included, whatever G (slices of one entry and empty slices included)."""
     monkeypatch.setenv("CCMI_LINK_G", str(G))
     D = _distances(n, seed, ties)
@@ -125,7 +125,7 @@ def _method_case(n, seed, method):
 @pytest.mark.parametrize("n,seed", [(257, 1), (2000, 3)])
 @pytest.mark.parametrize("method", ["complete", "weighted", "ward"])
 def test_grid_linkage_every_method_equals_oracle(method, n, seed, G, monkeypatch):
-    """The methods that test_grid_linkage_equals_oracle leaves out, in the one-workgroup kernel
+    """The methods that test_grid_linkage_equals_oracle leaves out, in one workgroup (G = 0)
     and on 2 and 16 workgroups.  Ward is the one update that reads size[i], of which every
     workgroup of the grid form keeps a private copy; it is the route of a one-tree budget of the
     hierarchical base clusterer."""
@@ -133,6 +133,42 @@ def test_grid_linkage_every_method_equals_oracle(method, n, seed, G, monkeypatch
     D, want = _method_case(n, seed, method)
     got = engine.linkage_raw(torch.from_numpy(D.copy()).cuda(), method).cpu().numpy()
     np.testing.assert_array_equal(got, want)
+
+
+def _refused_then_clean(D):
+    """linkage_raw refuses D with the no-neighbour error; the next call of the same process, on
+    finite distances, is untouched by it (the header with the error word is zeroed per launch)."""
+    from consensus_clustering_amd import _lib
+
+    with pytest.raises(_lib.CCMIError, match="found no neighbour"):
+        engine.linkage_raw(torch.from_numpy(D).cuda(), "average")
+    F, want = _method_case(257, 1, "average")
+    got = engine.linkage_raw(torch.from_numpy(F.copy()).cuda(), "average").cpu().numpy()
+    np.testing.assert_array_equal(got, want)
+
+
+@pytest.mark.parametrize("G", [0, 2])
+def test_linkage_refuses_a_one_element_chain_without_neighbour(G, monkeypatch):
+    """n = 3 with every off-diagonal distance +inf: the first scan finds nothing, and the -1 of the
+    one-element chain is never used as an index; cc_linkage_check reports the tree."""
+    monkeypatch.setenv("CCMI_LINK_G", str(G))
+    D = np.full((3, 3), np.inf)
+    np.fill_diagonal(D, 0.0)
+    _refused_then_clean(D)
+
+
+@pytest.mark.parametrize("G", [0, 2, 16])
+def test_linkage_refuses_an_unreachable_point(G, monkeypatch):
+    """n = 257 with point 100 at +inf from every other: the others merge among themselves for many
+    steps, point 100 is nobody's neighbour, and the scan that starts from it (or is left with it
+    alone) finds no finite neighbour; its sentinel is never used as an index.  Every workgroup of the grid form leaves on the same reduced values (at G = 16 most
+    slices do not hold index 100)."""
+    monkeypatch.setenv("CCMI_LINK_G", str(G))
+    D = _distances(257, 1, True).copy()
+    D[100, :] = np.inf
+    D[:, 100] = np.inf
+    D[100, 100] = 0.0
+    _refused_then_clean(D)
 
 
 def test_grid_linkage_while_another_stream_is_busy(monkeypatch):

@@ -23,7 +23,7 @@ for line in out.splitlines():
         rows.append(cur)
     elif cur is not None:
         cur[k] = v
-cols = ["VGPRs", "AGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]"]
+cols = ["VGPRs", "AGPRs", "TotalSGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]"]
 print("kernel | " + " | ".join(cols))
 for r in rows:
     print(r["kernel"][:90], "|", " | ".join(r.get(c, "-") for c in cols))
