@@ -45,7 +45,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import dist, engine, post
+from . import _lib, dist, engine, post
 from ._hostfit import fit_predict_chunk, fit_predict_one, subset
 from .kmeans import BatchedKMeans
 
@@ -890,4 +890,15 @@ def _prepare(X, dev):
 
     if not isinstance(X, torch.Tensor) and X.dtype.kind != 'f':
         X = np.asarray(X, dtype=np.float64)
-    return prepare_rows(X, dev)
+    try:
+        return prepare_rows(X, dev)
+    except _lib.CCMIError as e:
+        # cc_prepare_rows refuses non-finite rows before any fit is launched; host arrays and
+        # device tensors alike get check_array's message (X is read again on this path only)
+        if "non-finite" not in str(e):
+            raise
+        Xt = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.asarray(X))
+        if bool(torch.isnan(Xt).any()):
+            raise ValueError("Input X contains NaN.") from e
+        dt = str(Xt.dtype).replace("torch.", "")
+        raise ValueError(f"Input X contains infinity or a value too large for dtype('{dt}').") from e

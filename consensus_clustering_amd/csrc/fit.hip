@@ -58,10 +58,13 @@ __global__ void colmean_kernel(const double* __restrict__ part, int nb, int n, i
 }
 
 // centred, zero-padded rows, squared norms (sequential fma over the features) and per-block
-// max |x| (order-free)
+// max |x| (order-free).  A NaN or an infinity among the centred values (a non-finite input, or
+// inf - inf against an infinite column mean) makes the block's maximum +inf, which
+// cc_prepare_rows refuses: for device-resident X and the C ABI this is the only guard.
 __global__ void centre_kernel(const float* __restrict__ X, int n, int d, int dpad, const float* __restrict__ mean,
                               float* __restrict__ Xd, float* __restrict__ xnorm, float* __restrict__ amax_part) {
   __shared__ float red[256];
+  constexpr float INF = __builtin_huge_valf();
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   float am = 0.f;
   if (r < n) {
@@ -70,7 +73,7 @@ __global__ void centre_kernel(const float* __restrict__ X, int n, int d, int dpa
       const float v = k < d ? X[static_cast<size_t>(r) * d + k] - mean[k] : 0.f;
       Xd[static_cast<size_t>(r) * dpad + k] = v;
       q = fmaf(v, v, q);
-      am = fmaxf(am, fabsf(v));
+      am = fmaxf(am, isfinite(v) ? fabsf(v) : INF);  // fmaxf alone drops a NaN operand
     }
     xnorm[r] = q;
   }

@@ -564,7 +564,11 @@ __device__ void apply_changes(const KArgs& a, const int32_t* idx, const uint2* l
   const bool dok = lane * DL < DP;
   const int d0 = dok ? lane * DL : 0;
   for (int e = lane; e < K * DP; e += 64) acc[e] = 0.f;
+  // every cluster's count, not the first 64: a sparse item's slots keep whatever an earlier sweep
+  // counted there (its M-step wrote no counts), and K goes to 127
   if (lane < K) cnt[lane] = 0u;
+  static_assert(KMAX <= 128, "two counts per lane cover every cluster");
+  if (lane + 64 < K) cnt[lane + 64] = 0u;
   for (int sg = 0; sg < (full ? 1 : NW); ++sg) {
     const int n = full ? a.m : static_cast<int>(nseg[sg]);
     const uint2* ls = lst + static_cast<size_t>(sg) * a.lseg;
@@ -2358,7 +2362,10 @@ __global__ void split_kernel(const float* X, long long total, int dpad, float sc
   if (i >= total) return;
   const long long row = i / dpad;
   const int d = static_cast<int>(i - row * dpad);
-  const float xs = X[i] * scale;
+  float xs = X[i] * scale;
+  // keep the product apart from the conversion: fused, it becomes v_fma_mixlo_f16(scale, x, +0),
+  // which turns a -0 row value into a +0 hi (and the lo of that into -0)
+  asm volatile("" : "+v"(xs));
   const _Float16 hi = static_cast<_Float16>(xs);
   const _Float16 lo = static_cast<_Float16>(xs - static_cast<float>(hi));
   Xhl[row * 2 * dpad + d] = __builtin_bit_cast(uint16_t, hi);

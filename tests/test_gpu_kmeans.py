@@ -70,6 +70,40 @@ def test_labels_match_sklearn(n, d, k_true, Ks, H):
     assert np.all(np.isfinite(inert))
 
 
+@pytest.mark.parametrize("n,d,engine_name", [
+    (300, 20, "dpad 32"),
+    (600, 100, "dpad 128, sparse M-step"),
+    (300, 150, "wide"),
+])
+def test_power_of_two_scaling_changes_nothing(n, d, engine_name):
+    """X 2^s for s = +40, -40.  The scaling is exact in float32 and max |Xd| scales exactly, so the
+    scale exponent moves by -s (10 -> -30 and 50, inside the clamp) and the f16 operand image is
+    bit-identical; every reduction in the engines has a fixed order and tol is relative to the
+    data's variance.  So labels and n_iter are bit-identical to the unscaled run and the inertia
+    is the unscaled one times 2^(2 s) exactly.  A failure means an absolute constant (an epsilon,
+    a tolerance, an error bound) or a mishandled exponent somewhere in the engine."""
+    dev = engine.require_gpu()
+    X = blobs(n, d, 5, seed=n + d)
+    Ks, H, seed = [2, 5, 9], 3, 7
+    Xhl0, e0 = prepare_rows(X, dev)[3:]
+    idx, labs, inert, nit, stats = run_gpu(X, Ks, H, 0.8, seed)
+    assert stats[0] > 0 and np.all(inert > 0)
+    if d == 100:
+        assert stats[6] > 0  # the sparse M-step ran
+    for s in (40, -40):
+        Xs = X * np.float32(2.0 ** s)
+        assert np.array_equal(Xs.astype(np.float64), X.astype(np.float64) * 2.0 ** s)  # exact
+        Xhl, e = prepare_rows(Xs, dev)[3:]
+        assert e == e0 - s and -62 < e < 62, (e0, e, s)
+        assert torch.equal(Xhl, Xhl0), f"s={s}: f16 image"
+        idx_s, labs_s, inert_s, nit_s, _ = run_gpu(Xs, Ks, H, 0.8, seed)
+        np.testing.assert_array_equal(idx_s, idx)
+        np.testing.assert_array_equal(labs_s, labs, err_msg=f"{engine_name} s={s}: labels")
+        np.testing.assert_array_equal(nit_s, nit, err_msg=f"{engine_name} s={s}: n_iter")
+        np.testing.assert_array_equal(inert_s.astype(np.float64), inert.astype(np.float64) * 2.0 ** (2 * s),
+                                      err_msg=f"{engine_name} s={s}: inertia")
+
+
 def test_every_sampled_row_labelled_once():
     X = blobs(3000, 32, 5, seed=1)
     Ks = [2, 5, 9]

@@ -17,14 +17,16 @@ holds (DATA_SEED).  The exception is K = 2..30 on wide rows: no j in 0..59 is fr
 there, so j = 0 stays, whose K = 16 and K = 24 pass one near tie each on resample 0; identity is
 demanded of them all the same.
 
-The f16 engines' inertia is asserted finite and positive only; its largest relative difference
-to the float64 within-cluster sum of squares of the engine's own labels is printed per case."""
+The f16 engines' n_iter must equal sklearn's and their inertia must lie within the rounding bound
+of check_sklearn of the float64 sum of squares about sklearn's centres (fixtures fit_<case>.npz);
+the largest error in units of sigma is printed per case."""
 import numpy as np
 import pytest
 import torch
 
 from consensus_clustering_amd import engine, kmeans
 from consensus_clustering_amd.kmeans import BatchedKMeans
+from tests.conftest import digest
 from tests.sk_parity import load_sk_fixture, partition_ss, sklearn_identical, sklearn_parity
 from tests.test_gpu_kmeans import blobs, run_gpu
 
@@ -70,7 +72,11 @@ def fit(case, Ks, H, tag="default"):
 
 def check_sklearn(case, run, Ks, H):
     """Every (K, h) identical to sklearn's float32 labels; resample 0 also through the full
-    classification (which reads the fixture's variants and must find none needed)."""
+    classification (which reads the fixture's variants and must find none needed).  n_iter equals
+    sklearn's for every (K, h) on which sklearn's own float32 and float64 fits agree about it, and
+    the inertia lies within 8 sigma + 2^-19 relative of the float64 sum of squares about sklearn's
+    float32 centres (tests/golden/sk/fit_<case>.npz, make_sk_fit_fixtures.py: sigma is one float32
+    rounding per row at the magnitude of the cancelling terms, in quadrature)."""
     X = rows(case)
     idx, labs, inert, nit, stats = run
     assert sklearn_identical(case, X, labs, idx) == len(Ks) * H
@@ -85,7 +91,22 @@ def check_sklearn(case, run, Ks, H):
         for h in range(H):
             ss = partition_ss(X[idx[h]], labs[k, h], K)
             rel = max(rel, abs(float(inert[k, h]) - ss) / ss)
-    print(f"f16 inertia [{case}, {len(Ks)} K x {H}]: max |inertia - SS64(own labels)| / SS64 = {rel:.3e}")
+    f = load_sk_fixture("fit_" + case)
+    meta = f["meta"]
+    assert (meta["Ks"], meta["H"], meta["seed"], meta["frac"]) == (list(Ks), H, SEED, FRAC)
+    assert meta["x_sha256"] == digest(X)
+    err = np.abs(inert.astype(np.float64) - f["inertia64"]) / f["inertia64"]
+    bound = 8.0 * f["sigma"] + 2.0 ** -19
+    worst = np.unravel_index(np.argmax(err / bound), err.shape)
+    print(f"f16 inertia [{case}, {len(Ks)} K x {H}]: max |inertia - SS64(own labels)| / SS64 = {rel:.3e}; against "
+          f"sklearn's centres max |err| / sigma = {(err / f['sigma']).max():.2f}, max |err| / inertia64 = {err.max():.3e}, "
+          f"max |err| / bound = {(err / bound).max():.3f} at K = {Ks[worst[0]]}, h = {worst[1]}; n_iter "
+          f"{int(nit.min())}..{int(nit.max())}, {int((nit != f['n_iter']).sum())} differ from sklearn's, "
+          f"{int(f['exempt'].sum())} exempt")
+    differ = [(Ks[k], h, int(nit[k, h]), int(f["n_iter"][k, h])) for k, h in np.argwhere((nit != f["n_iter"]) & ~f["exempt"])]
+    assert not differ, f"n_iter (K, h, engine, sklearn): {differ}"
+    over = [(Ks[k], h, float(err[k, h]), float(bound[k, h])) for k, h in np.argwhere(err > bound)]
+    assert not over, f"inertia (K, h, relative error, bound): {over}"
 
 
 def triple(run, k=None):
@@ -109,6 +130,18 @@ def test_narrow_bigk_identical_to_sklearn(d):
     check_sklearn(case, run, BIGK, 3)
     if d == 100:
         assert run[4][6] > 0  # the sparse M-step ran at these K
+
+
+def test_narrow_bigk_dense_mstep_identical_to_sklearn(monkeypatch):
+    """d = 100 with the sparse M-step switched off (CCMI_KM_DENSE=1): the same checks, so that
+    neither form of the M-step hides behind the other.  (The sparse form once left the counts of
+    clusters 64 and up of a change-list sweep uncleared: K = 65, h = 0 converged on a centre
+    scaled by a stale count, with sklearn's labels and n_iter and an inertia 6.2e-3 too high.)"""
+    case = "bigk_n1536_d100"
+    monkeypatch.setenv("CCMI_KM_DENSE", "1")
+    run = fit(case, BIGK, 3, tag="dense")
+    assert run[4][6] == 0
+    check_sklearn(case, run, BIGK, 3)
 
 
 def test_narrow_unit_split_changes_nothing(monkeypatch):
