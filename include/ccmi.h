@@ -101,7 +101,11 @@ int cc_resample_device_wide(uint32_t seed, int h_begin, int h_end, int n, int m,
 size_t cc_resample_device_wide_workspace_bytes(int n, int nh);
 
 /* labels_nh[idx[h][r] * ldl + h] = labels_hm ? labels_hm[h*m + r] : 0 for h < H, r < m.
- * labels_nh must be pre-filled with 0xFF (= not sampled).  (CC.py:260-262, :284-285) */
+ * labels_nh must be pre-filled with 0xFF (= not sampled).  (CC.py:260-262, :284-285)
+ * An entry of idx_hm outside [0, n) addresses no row: it is skipped, nothing is written for it
+ * and the call still returns CC_OK.  Only the low byte of a label is stored.  H = 0 or m = 0
+ * writes nothing (CC_OK); ldl < H, n <= 0, a negative H or m, or a NULL idx_hm / labels_nh is
+ * CC_ERR_ARG.  Asynchronous on `stream`. */
 int cc_scatter_labels(const int32_t* idx_hm, const int32_t* labels_hm, int H, int m, int n,
                       int8_t* labels_nh, int ldl, void* stream);
 
