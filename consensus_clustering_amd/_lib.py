@@ -73,6 +73,12 @@ SIGNATURES = {
     "cc_hc_check": (_c_int, [_vp, _c_int, _vp]),
     "cc_hc_cut": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _c_i64, _c_i64,
                            _vp, _c_sz, _vp]),
+    "cc_pam_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int, _c_int]),
+    "cc_pam_build": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _c_sz, _vp]),
+    "cc_pam_swap_step": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_sz, _vp]),
+    "cc_pam_active": (_c_int, [_vp, _vp, _vp]),
+    "cc_pam_labels": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_i64, _c_i64, _vp,
+                               _vp, _c_i64, _vp, _vp, _c_sz, _vp]),
     "cc_kmeans_f64_workspace_bytes": (_c_sz, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int]),
     "cc_kmeans_f64": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp,
                                _c_int, _c_int, _c_int, _c_dbl, _vp, _c_int, _vp, _vp, _c_int, _vp,

@@ -19,7 +19,9 @@ What runs where (``fit``):
                   cc_hc_cut; ``hierarchical``), with ``feature_subsampling`` < 1 from each
                   resample's own columns (cc_pdist_batched); any other plugin clusterer
                   (e.g. GaussianMixture) keeps the reference's host fit_predict per
-                  (K, h) and only its labels go to the GPU (hybrid path)
+                  (K, h) and only its labels go to the GPU (hybrid path); PAM (pam.py, k-medoids
+                  under the same four metrics) -> BUILD and SWAP of every (resample, K) on the
+                  device over the same distances (cc_pam_build, cc_pam_swap_step, cc_pam_labels)
   I, M, histogram int8-MFMA tiles of the upper triangle (cc_cosample / cc_coassoc)
   hist/cdf/PAC    host float64 from 20 exact integer counts (post.py)
   multi-GPU       resamples and triangle tiles sharded over torch.distributed ranks
@@ -48,6 +50,9 @@ import torch
 from . import _lib, dist, engine, post
 from ._hostfit import fit_predict_chunk, fit_predict_one, subset
 from .kmeans import BatchedKMeans
+from .pam import METRICS as HC_METRICS  # sklearn's metric spellings -> scipy's names
+from .pam import PAM, degenerate_rows as _hc_degenerate, refuse_not_finite
+from .pam import validate as _pam_validate
 
 KMAX = 127  # largest K: uint8 labels (0xFF = not sampled) and int8 one-hot channels
 
@@ -73,10 +78,6 @@ def _is_default_kmeans(est) -> bool:
 
 
 HC_LINKAGES = ('ward', 'average', 'complete')
-
-
-HC_METRICS = dict(euclidean='euclidean', l2='euclidean', manhattan='cityblock', l1='cityblock',
-                  cityblock='cityblock', cosine='cosine', correlation='correlation')
 
 
 PRECISIONS = ('auto', 'f64', 'fast')
@@ -142,21 +143,6 @@ def _is_device_hierarchical(est) -> bool:
     return _hc_linkage(est) is not None
 
 
-def _hc_degenerate(X, metric):
-    """Why pdist(X, metric) has a row without distances, or None, from the host array X: an
-    all-zero row under cosine (sklearn's own refusal, in its words) and a constant row under
-    correlation (it centres to zero, so its distances are 0 / 0)."""
-    if metric == "cosine":
-        if np.any(~np.any(X, axis=1)):
-            return "Cosine affinity cannot be used when X contains zero vectors"
-    elif metric == "correlation":
-        const = np.flatnonzero((X == X[:, :1]).all(axis=1))
-        if const.size:
-            return (f"the correlation metric cannot be used when X contains constant rows (row {int(const[0])} "
-                    "is constant: its correlation distances are undefined)")
-    return None
-
-
 def _hc_route(spec, X, hierarchical, degenerate_test=True):
     """The (linkage, metric) the device trees run, or None for the host loop, from the estimator's
     _hc_spec, the host array X and the ``hierarchical`` keyword; decided from host values alone,
@@ -190,10 +176,7 @@ def _hc_validate(X, m, Ks):
     resample, and a K above the resample size (_hc_cut's message)."""
     if X is not None:
         X = np.asarray(X)
-        if X.dtype.kind == 'f' and not np.isfinite(X).all():
-            if np.isnan(X).any():
-                raise ValueError("Input X contains NaN.")
-            raise ValueError(f"Input X contains infinity or a value too large for dtype('{X.dtype}').")
+        refuse_not_finite(X)
         d = X.shape[1] if X.ndim == 2 else 0
     else:
         d = 0
@@ -204,6 +187,35 @@ def _hc_validate(X, m, Ks):
         if K > m:
             raise ValueError("Cannot extract more clusters than samples: "
                              f"{K} clusters were given for a tree with {m} leaves.")
+
+
+def _pam_spec(est):
+    """scipy's name of the metric of a PAM that the device reproduces (cc_pam_build,
+    cc_pam_swap_step, cc_pam_labels), else None: exactly that type (a subclass may override
+    anything), a metric of HC_METRICS and an integer max_iter >= 0."""
+    if type(est) is not PAM:
+        return None
+    p = est.get_params()
+    metric, max_iter = p.get("metric"), p.get("max_iter")
+    if not isinstance(metric, str) or metric not in HC_METRICS:
+        return None
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 0:
+        return None
+    return HC_METRICS[metric]
+
+
+def _pam_route(metric, X):
+    """The metric the device PAM runs, or None for the host loop, from _pam_spec and host values
+    alone, so every rank decides alike before any launch.  A degenerate row of X
+    (_hc_degenerate) keeps the fit in the host loop, where PAM raises only if a resample
+    contains the row: the rule of the device trees under hierarchical='auto'.  X None (feature
+    subsampling: engine.pam_labels tests every resample's own rows under its own columns)
+    leaves that test out."""
+    if metric in ('cosine', 'correlation') and X is not None:
+        Xh = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
+        if _hc_degenerate(Xh, metric) is not None:
+            return None
+    return metric
 
 
 class ConsensusClustering:
@@ -344,6 +356,7 @@ class ConsensusClustering:
         self.labels_ = self._idx_dev = self._idx_host = None
         self.kmeans_inertia_ = self.kmeans_n_iter_ = self.kmeans_stats_ = None
         self.hc_stats_ = self.hc_metric_ = None
+        self.pam_stats_ = self.pam_metric_ = self.pam_inertia_ = self.pam_n_iter_ = None
         if self.hierarchical not in ('auto', 'device', 'host'):
             raise ValueError("hierarchical must be 'auto', 'device' or 'host'")
         self.partial_ = False
@@ -413,7 +426,11 @@ class ConsensusClustering:
             hc = _hc_route(spec, Xh, self.hierarchical)
         elif self.hierarchical == 'device':
             _hc_route(None, None, 'device')
-        self.backend_ = 'gpu-kmeans' if km is not None else ('gpu-hc' if hc is not None else 'host-clusterer')
+        pam = None
+        if Ks and km is None and hc is None:
+            pam = _pam_route(_pam_spec(self.clusterer), X if cols is None else None)
+        self.backend_ = ('gpu-kmeans' if km is not None else 'gpu-hc' if hc is not None
+                         else 'gpu-pam' if pam is not None else 'host-clusterer')
         precision = self.precision
         if precision == 'auto':
             # the reference's clusterer computes in X's dtype (CC.py:282): float64 input keeps
@@ -450,6 +467,11 @@ class ConsensusClustering:
             self.hc_metric_ = hc[1]
             self.hc_stats_ = self._fit_hierarchical(X, wdtype, hc[0], hc[1], idx_d, n, m, h0, h1, Ks, labels, dev,
                                                     cols=cols)
+        elif Ks and pam is not None:
+            self.pam_metric_ = pam
+            self.pam_inertia_ = torch.zeros((len(Ks), H), dtype=torch.float64, device=dev)
+            self.pam_n_iter_ = torch.zeros((len(Ks), H), dtype=torch.int32, device=dev)
+            self.pam_stats_ = self._fit_pam(X, wdtype, pam, idx_d, n, m, h0, h1, Ks, labels, dev, cols=cols)
         elif Ks:
             if isinstance(X, torch.Tensor):
                 X = X.cpu().numpy()
@@ -537,38 +559,62 @@ class ConsensusClustering:
         tensor X stays there for every metric).  A resample that holds a row without distances
         under its columns raises ValueError, as sklearn does in the host loop; the ranks agree on
         the lowest such resample before the label exchange (dist.first_failure), so all raise."""
+        nh = max(h1 - h0, 1)
+        return self._fit_on_distances(
+            X, wdtype, metric, n, m, Ks, dev, cols, _hc_validate,
+            lambda budget, md: engine.hc_plan(n, m, nh, len(Ks), budget, md=md),
+            lambda Dfull, Xd, cols_d, budget: engine.hc_labels(Dfull, idx_d, h0, h1, Ks, link, labels, budget=budget,
+                                                               X=Xd, cols_d=cols_d, metric=metric))
+
+    def _fit_pam(self, X, wdtype, metric, idx_d, n, m, h0, h1, Ks, labels, dev, cols=None):
+        """CC.py:282 for PAM(metric=metric, max_iter=...) on the device: the distances as
+        _fit_hierarchical takes them (the n x n matrix once, or each resample's own under feature
+        subsampling), then BUILD and SWAP of every (resample, K) of [h0, h1) into this rank's
+        columns of the label matrix, of pam_inertia_ and of pam_n_iter_ (engine.pam_labels)."""
+        nh = max(h1 - h0, 1)
+        max_iter = int(self.clusterer.get_params()["max_iter"])
+        return self._fit_on_distances(
+            X, wdtype, metric, n, m, Ks, dev, cols, _pam_validate,
+            lambda budget, md: engine.pam_plan(n, m, nh, len(Ks), max(Ks), budget, md=md),
+            lambda Dfull, Xd, cols_d, budget: engine.pam_labels(Dfull, idx_d, h0, h1, Ks, labels, budget=budget,
+                                                                max_iter=max_iter, X=Xd, cols_d=cols_d, metric=metric,
+                                                                inertia=self.pam_inertia_, n_iter=self.pam_n_iter_))
+
+    def _fit_on_distances(self, X, wdtype, metric, n, m, Ks, dev, cols, validate, plan, run):
+        """What the device clusterers over pdist(X, metric) share (the trees and PAM): the
+        refusals of validate(X, m, Ks) from host values, plan(budget, md) when a workspace_budget
+        is set (too small: raises before any launch), the distances, and run(Dfull, Xd, cols_d,
+        budget) -> stats: with Dfull (float64 [n, n], device) and the rest None, or under feature
+        subsampling with Dfull None, the rows Xd on the device and the columns cols_d [H, md]; a
+        DegenerateResample of run is then agreed on by the ranks (dist.first_failure)."""
         if isinstance(X, torch.Tensor):
             # a device tensor: the finiteness test runs where X lives (torch, no kernel of ours)
-            _hc_validate(None if bool(torch.isfinite(X).all()) else X.detach().cpu().numpy(), m, Ks)
+            validate(None if bool(torch.isfinite(X).all()) else X.detach().cpu().numpy(), m, Ks)
             Xd = X.to(dev, torch.float64 if wdtype == np.float64 else torch.float32).contiguous()
         else:
-            _hc_validate(X, m, Ks)
+            validate(X, m, Ks)
             Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=wdtype)).to(dev)
         budget = self.workspace_budget
+        if budget is not None:
+            plan(budget, None if cols is None else cols.shape[1])  # too small: raises before any launch
         if cols is not None:
-            md = cols.shape[1]
-            if budget is not None:
-                engine.hc_plan(n, m, max(h1 - h0, 1), len(Ks), budget, md=md)  # too small: raises before any launch
             cols_d = torch.from_numpy(cols).to(dev)
             stats = code = None
             try:
-                stats = engine.hc_labels(None, idx_d, h0, h1, Ks, link, labels, budget=budget, X=Xd,
-                                         cols_d=cols_d, metric=metric)
+                stats = run(None, Xd, cols_d, budget)
             except engine.DegenerateResample as e:
                 code = e.code
             code = dist.first_failure(code, dev)
             if code is not None:
                 raise engine.DegenerateResample(code, metric)
             return stats
-        if budget is not None:
-            engine.hc_plan(n, m, max(h1 - h0, 1), len(Ks), budget)  # too small: raises before any launch
         Dfull = engine.euclidean(Xd) if metric == 'euclidean' else engine.pdist(Xd, metric)
         if not bool(torch.isfinite(Dfull).all()):  # finite X can still overflow the squares
             if metric == 'euclidean':
                 raise ValueError("the euclidean distances between the rows of X are not all finite "
                                  "(overflow in float64)")
             raise ValueError(f"the {metric} distances between the rows of X are not all finite")
-        return engine.hc_labels(Dfull, idx_d, h0, h1, Ks, link, labels, budget=budget)
+        return run(Dfull, None, None, budget)
 
     def _check_k_range(self, Ks):
         """Every K of K_range must be an integer in [1, 127] (the uint8 label format and the

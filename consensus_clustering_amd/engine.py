@@ -578,6 +578,27 @@ def hc_feature_bytes(m: int, md: int) -> int:
     return 8 * int(m) * int(md) + 8 * int(m) + 4 * int(md)
 
 
+def _trees_per_batch(per: int, n: int, m: int, nh: int, budget: int, md, who: str) -> int:
+    """min(nh, the trees of `per` bytes each that fit the budget next to the n x n distances);
+    with md (feature subsampling) there is no n x n matrix and a tree needs hc_feature_bytes more.
+    Raises when not one tree fits."""
+    if md is not None:
+        per += hc_feature_bytes(m, md)
+        fit = int(budget) // per
+        if fit < 1:
+            raise ValueError(
+                f"workspace_budget = {int(budget)} bytes cannot hold the {who} clusterer: one tree "
+                f"of m = {int(m)} over {int(md)} features ({per} bytes) is needed")
+    else:
+        fit = (int(budget) - 8 * int(n) * int(n)) // per
+        if fit < 1:
+            raise ValueError(
+                f"workspace_budget = {int(budget)} bytes cannot hold the {who} clusterer: the n x n "
+                f"float64 distances ({8 * int(n) * int(n)} bytes) and one tree of m = {int(m)} "
+                f"({per} bytes) are needed")
+    return max(1, min(int(nh), int(fit)))
+
+
 def hc_plan(n: int, m: int, nh: int, nK: int, budget: int, md: int = None):
     """(B, route) for the nh resamples of a rank: B = min(nh, (budget - 8 n^2) // bytes per tree)
     trees per launch; route 'batched' (cc_hc_nnchain_batched on B trees) or 'sequential' (one
@@ -588,24 +609,31 @@ def hc_plan(n: int, m: int, nh: int, nK: int, budget: int, md: int = None):
     md (feature subsampling: every tree computes its own distances from md columns,
     cc_pdist_batched): there is no n x n matrix, so the budget holds no 8 n^2 term, and a tree
     needs hc_feature_bytes(m, md) more."""
-    per = hc_tree_bytes(m, nK)
-    if md is not None:
-        per += hc_feature_bytes(m, md)
-        fit = int(budget) // per
-        if fit < 1:
-            raise ValueError(
-                f"workspace_budget = {int(budget)} bytes cannot hold the hierarchical clusterer: one tree "
-                f"of m = {int(m)} over {int(md)} features ({per} bytes) is needed")
-    else:
-        fit = (int(budget) - 8 * int(n) * int(n)) // per
-        if fit < 1:
-            raise ValueError(
-                f"workspace_budget = {int(budget)} bytes cannot hold the hierarchical clusterer: the n x n "
-                f"float64 distances ({8 * int(n) * int(n)} bytes) and one tree of m = {int(m)} "
-                f"({per} bytes) are needed")
-    B = max(1, min(int(nh), int(fit)))
+    B = _trees_per_batch(hc_tree_bytes(m, nK), n, m, nh, budget, md, "hierarchical")
     route = 'sequential' if B < min(int(nh), HC_BATCH_CROSSOVER) else 'batched'
     return B, route
+
+
+def _resample_batches(Dfull, idx_d, h0, h1, B, X=None, cols_d=None, metric=None):
+    """(a, rows, D) for the resamples [a, a + len(rows)) of [h0, h1), B at a time: rows = idx_d's
+    rows and D [len(rows), m, m] their distances in one buffer that every batch reuses, gathered
+    from Dfull (cc_hc_gather) or, with Dfull None, computed from each resample's own columns
+    (cc_pdist_batched), where a batch that holds a degenerate resample raises DegenerateResample
+    before it is handed out."""
+    m = idx_d.shape[1]
+    dev = X.device if Dfull is None else Dfull.device
+    Db = torch.empty((B, m, m), dtype=torch.float64, device=dev)
+    for a in range(h0, h1, B):
+        b = min(a + B, h1)
+        rows = idx_d[a:b].contiguous()
+        if Dfull is None:
+            D, norms = _pdist_batched(X, rows, cols_d[a:b].contiguous(), metric, out=Db[:b - a])
+            code = _degenerate_code(D, norms, a)
+            if code is not None:
+                raise DegenerateResample(code, metric)
+        else:
+            D = hc_gather(Dfull, rows, out=Db[:b - a])
+        yield a, rows, D
 
 
 def hc_labels(Dfull: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, method: str,
@@ -649,22 +677,124 @@ def hc_labels(Dfull: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, me
         return stats
     Ks_d = torch.tensor([int(K) for K in Ks], dtype=torch.int32, device=dev)
     ws = hc_workspace(m, B, nK, dev)
-    Db = torch.empty((B, m, m), dtype=torch.float64, device=dev)
-    for a in range(h0, h1, B):
-        b = min(a + B, h1)
-        rows = idx_d[a:b].contiguous()
-        if feature:
-            D, norms = _pdist_batched(X, rows, cols_d[a:b].contiguous(), metric, out=Db[:b - a])
-            code = _degenerate_code(D, norms, a)
-            if code is not None:
-                raise DegenerateResample(code, metric)
-        else:
-            D = hc_gather(Dfull, rows, out=Db[:b - a])
+    for a, rows, D in _resample_batches(Dfull, idx_d, h0, h1, B, X, cols_d, metric):
         if route == 'batched':
             Z = hc_nnchain_batched(D, method, ws)
         else:
             with timed("cc_linkage_nnchain"):
                 Z = linkage_raw(D[0], method).unsqueeze(0)
         hc_cut(Z, rows, Ks_d, a, labels, ws)
+        stats['launches'] += 1
+    return stats
+
+
+# ---------------------------------------------------------------- PAM base clusterer
+
+def pam_tree_bytes(m: int, nK: int, Kmax: int) -> int:
+    """Device bytes one tree of a PAM batch needs: its m x m float64 distances, the BUILD state
+    (score, near, medoid flags, the chain) and per K the SWAP state (near and second in item and
+    in slot order, the best dTD per candidate, slots, the grouping, its medoids and segment
+    offsets); cc_pam_workspace_bytes plus the distances."""
+    m, nK, Kmax = int(m), int(nK), int(Kmax)
+    per_k = (5 * 8 + 3 * 4) * m + 4 * (2 * Kmax + 1) + 8
+    return 8 * m * m + (8 + 8 + 4) * m + 4 * Kmax + nK * per_k + 256 * (6 + 12)  # 256: alignment of each part
+
+
+def pam_plan(n: int, m: int, nh: int, nK: int, Kmax: int, budget: int, md: int = None) -> int:
+    """B = min(nh, (budget - 8 n^2) // bytes per tree) trees per batch for the nh resamples of a
+    rank, as hc_plan counts them (md: feature subsampling, no n x n matrix, hc_feature_bytes more
+    per tree).  Raises when the distances and one tree do not fit the budget."""
+    return _trees_per_batch(pam_tree_bytes(m, nK, Kmax), n, m, nh, budget, md, "PAM")
+
+
+def pam_batch(D: torch.Tensor, rows: torch.Tensor, Ks_d: torch.Tensor, Kmax: int, h_begin: int,
+              labels: torch.Tensor, max_iter: int = 300, inertia: torch.Tensor = None,
+              n_iter: torch.Tensor = None, medoids: torch.Tensor = None, ws: torch.Tensor = None) -> int:
+    """PAM of every (tree b, K) over the distances D [B, m, m] (float64, device, read only):
+    cc_pam_build, then cc_pam_swap_step until cc_pam_active reads 0 or max_iter iterations ran,
+    then cc_pam_labels into labels[k, rows[b, r], h_begin + b] (uint8 [nK, n, Hpad]), inertia and
+    n_iter ([nK, H], at column h_begin + b) and medoids (int32 [B, nK, Kmax], ascending, -1 padded).
+    Ks_d: int32 [nK] on the device, every K in [1, Kmax], Kmax <= min(m, 127).  Returns the number
+    of SWAP iterations launched."""
+    assert D.dtype == torch.float64 and D.dim() == 3 and D.shape[1] == D.shape[2] and D.is_contiguous()
+    B, m, _ = D.shape
+    nK = Ks_d.numel()
+    assert rows.dtype == torch.int32 and tuple(rows.shape) == (B, m) and rows.is_contiguous()
+    assert Ks_d.dtype == torch.int32 and Ks_d.is_cuda and Ks_d.is_contiguous()
+    assert labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous() and labels.shape[0] == nK
+    ldo = 0
+    for t, dt in ((inertia, torch.float64), (n_iter, torch.int32)):
+        if t is not None:
+            assert t.dtype == dt and t.dim() == 2 and t.shape[0] == nK and t.is_contiguous()
+            ldo = t.shape[1]
+    if inertia is not None and n_iter is not None:
+        assert inertia.shape == n_iter.shape
+    if medoids is not None:
+        assert medoids.dtype == torch.int32 and tuple(medoids.shape) == (B, nK, Kmax) and medoids.is_contiguous()
+    dev = D.device
+    if ws is None:
+        ws = pam_workspace(m, B, nK, Kmax, dev)
+    st = stream_ptr(dev)
+    with timed("cc_pam_build"):
+        _lib.call("cc_pam_build", D.data_ptr(), B, m, Ks_d.data_ptr(), nK, int(Kmax), ws.data_ptr(), ws.numel(), st)
+    iterations = 0
+    active = ctypes.c_int(0)
+    with timed("cc_pam_swap"):
+        while iterations < int(max_iter):
+            _lib.call("cc_pam_swap_step", D.data_ptr(), B, m, Ks_d.data_ptr(), nK, int(Kmax), int(max_iter),
+                      ws.data_ptr(), ws.numel(), st)
+            _lib.call("cc_pam_active", ws.data_ptr(), ctypes.addressof(active), st)
+            iterations += 1
+            if active.value == 0:
+                break
+    with timed("cc_pam_labels"):
+        _lib.call("cc_pam_labels", D.data_ptr(), rows.data_ptr(), B, m, Ks_d.data_ptr(), nK, int(Kmax), int(h_begin),
+                  labels.data_ptr(), labels.shape[1], labels.shape[2], _lib.ptr(inertia), _lib.ptr(n_iter), ldo,
+                  _lib.ptr(medoids), ws.data_ptr(), ws.numel(), st)
+    return iterations
+
+
+def pam_workspace(m: int, B: int, nK: int, Kmax: int, device) -> torch.Tensor:
+    nbytes = int(_lib.load().cc_pam_workspace_bytes(int(m), int(B), int(nK), int(Kmax)))
+    if nbytes == 0:
+        raise ValueError(f"PAM on the device needs 1 <= K <= min(m, 127), m <= 65535 and at most 65535 trees a "
+                         f"batch, got m = {m}, B = {B}, nK = {nK}, max K = {Kmax}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def pam_labels(Dfull: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, labels: torch.Tensor,
+               budget: int = None, max_iter: int = 300, X: torch.Tensor = None, cols_d: torch.Tensor = None,
+               metric: str = None, inertia: torch.Tensor = None, n_iter: torch.Tensor = None) -> dict:
+    """Fill labels[k, idx[h, r], h] for h in [h0, h1) and every K of Ks with PAM(n_clusters=K,
+    max_iter=max_iter) over Dfull[idx[h]][:, idx[h]] (one BUILD chain per h serves every K).
+    Arguments as hc_labels, feature subsampling (Dfull None; X, cols_d, metric) and
+    DegenerateResample included; inertia / n_iter: optional [nK, H] device tensors filled at the
+    columns [h0, h1).  Returns dict(route='batched', batch, launches, swap_iterations)."""
+    feature = Dfull is None
+    if feature:
+        if X is None or cols_d is None or metric is None:
+            raise ValueError("without Dfull, pam_labels needs X, cols_d and metric")
+        n, dev, md = X.shape[0], X.device, cols_d.shape[1]
+    else:
+        n, dev, md = Dfull.shape[0], Dfull.device, None
+    m = idx_d.shape[1]
+    nh = h1 - h0
+    Ks = [int(K) for K in Ks]
+    nK = len(Ks)
+    Kmax = max(Ks) if Ks else 1
+    if budget is None:
+        budget = (0 if feature else 8 * n * n) + torch.cuda.mem_get_info(dev)[0] // 2
+    B = pam_plan(n, m, max(nh, 1), nK, Kmax, budget, md=md)
+    stats = dict(route='batched', batch=B, launches=0, swap_iterations=0)
+    if feature:
+        stats['feature_subsampling'] = md
+    if nh <= 0 or nK == 0:
+        return stats
+    if min(Ks) < 1 or Kmax > m:
+        raise ValueError(f"every K must lie in [1, m = {m}], got {Ks}")
+    Ks_d = torch.tensor(Ks, dtype=torch.int32, device=dev)
+    ws = pam_workspace(m, B, nK, Kmax, dev)
+    for a, rows, D in _resample_batches(Dfull, idx_d, h0, h1, B, X, cols_d, metric):
+        stats['swap_iterations'] += pam_batch(D, rows, Ks_d, Kmax, a, labels, max_iter, inertia, n_iter, ws=ws)
         stats['launches'] += 1
     return stats

@@ -36,6 +36,9 @@
  *                         correlation (average and complete linkage): scipy's pdist, bit for bit
  *   cc_pdist_batched      the same distances per resample when each resample also draws its own
  *                         columns (feature subsampling): pdist(X[idx[b]][:, cols[b]], metric)
+ *   cc_pam_build, cc_pam_swap_step, cc_pam_active, cc_pam_labels
+ *                         CC.py:282 for the PAM (k-medoids) base clusterer: BUILD and SWAP of
+ *                         every (resample, K) problem over the same [B][m][m] distances
  */
 #ifndef CCMI_H
 #define CCMI_H
@@ -299,6 +302,55 @@ int cc_hc_check(const void* workspace, int B, void* stream);
 int cc_hc_cut(const double* Z, const int* rank, const int* idx, int B, int m, const int* Ks, int nK,
               int h_begin, uint8_t* labels, int64_t n, int64_t ldl, void* workspace, size_t ws_bytes,
               void* stream);
+
+/* PAM (partitioning around medoids; Kaufman & Rousseeuw's BUILD and SWAP, R's pam with
+ * pamonce = 0) for the nK values Ks of K on each of B trees' distances D [B][m][m] (float64,
+ * symmetric, zero diagonal, finite; read only), the batch cc_hc_gather or cc_pdist_batched makes.
+ * Problem (b, k) has Ks[k] medoids.  Ks [nK] int32 on the device, 1 <= Ks[k] <= Kmax; a value
+ * outside is read as the nearest bound.  Limits: B <= 65535, m <= 65535, 1 <= Kmax <= min(m, 127).
+ * All arithmetic is float64 and no sum uses a floating-point atomic: the same inputs give the same
+ * medoids and bitwise the same inertia on every run.  A decision between two candidates whose
+ * sums differ by less than about m * 2^-52 of the sums may fall differently than in another
+ * conforming implementation, which adds in another order; on integer-valued distances every sum
+ * is exact and the tie rules below decide.
+ *
+ * cc_pam_workspace_bytes: the workspace of the calls below (0 for arguments they refuse).  One
+ * workspace carries a batch from cc_pam_build through cc_pam_swap_step to cc_pam_labels. */
+size_t cc_pam_workspace_bytes(int m, int B, int nK, int Kmax);
+
+/* BUILD: medoid 0 of a tree is the first index of the smallest row sum; step t = 1 .. Kmax - 1
+ * adds the first index of the largest gain sum_j max(near[j] - D[i][j], 0) over the non-medoids
+ * (near[j]: the distance of j to its nearest medoid so far).  The chain is greedy, so problem
+ * (b, k) starts from the first Ks[k] medoids of tree b's chain.  Two launches a step, ordered by
+ * the stream, then one that sets up every problem's state (near, second, nearest slot, the items
+ * grouped by slot, n_iter = 0).  Asynchronous on `stream`. */
+int cc_pam_build(const double* D, int B, int m, const int* Ks, int nK, int Kmax, void* workspace, size_t ws_bytes,
+                 void* stream);
+
+/* One SWAP iteration of every problem that is still active (after cc_pam_build every problem
+ * is): over all pairs of a medoid i and a non-medoid h, dTD(i, h) = sum_j of
+ * min(D[h][j], second[j]) - near[j] where i is j's nearest medoid, else min(D[h][j] - near[j], 0);
+ * the smallest is taken, a tie to the lowest h, then to the medoid with the lowest item index.
+ * When it is < 0 and the problem has made fewer than max_iter swaps, h replaces i and the state
+ * is refreshed; else the problem is converged and later calls leave it alone.  The number of
+ * problems that swapped is left in the workspace for cc_pam_active.  Asynchronous on `stream`. */
+int cc_pam_swap_step(const double* D, int B, int m, const int* Ks, int nK, int Kmax, int max_iter, void* workspace,
+                     size_t ws_bytes, void* stream);
+
+/* Synchronises `stream` and stores in *active (host) how many problems the last
+ * cc_pam_swap_step swapped: 0 = every problem is converged. */
+int cc_pam_active(const void* workspace, int* active, void* stream);
+
+/* The results of the batch: for tree b (resample h_begin + b), K index k and item r,
+ * labels[k][idx[b][r]][h_begin + b] = the rank, by ascending item index, of r's nearest medoid (a
+ * tie in distance goes to the lowest item index; a medoid labels itself); labels uint8
+ * [nK][n][ldl], idx [B][m] int32 as for cc_hc_cut.  inertia [nK][ldo] float64 and n_iter [nK][ldo]
+ * int32 (either may be NULL) receive at [k][h_begin + b] the total deviation sum_j near[j] and the
+ * number of swaps made; medoids (NULL or [B][nK][Kmax] int32) the medoid items r in ascending
+ * order, -1 behind the first Ks[k]. */
+int cc_pam_labels(const double* D, const int* idx, int B, int m, const int* Ks, int nK, int Kmax, int h_begin,
+                  uint8_t* labels, int64_t n, int64_t ldl, double* inertia, int* n_iter, int64_t ldo, int* medoids,
+                  void* workspace, size_t ws_bytes, void* stream);
 
 /* Batched k-means for every (resample h, K, init) problem, replacing the per-(K, h)
  * clusterer.fit_predict(X[indices]) of CC.py:282 for the default clusterer
