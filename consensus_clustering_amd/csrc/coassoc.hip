@@ -32,6 +32,10 @@
 // then the two edge corrections against the float32 edges.  Per-thread private
 // LDS counters (ds_add, conflict-free [bin][thread] layout) are reduced per
 // workgroup and added to 20 uint64 global counters (integer atomics: order-free).
+//
+// One kernel, tiles_kernel<KP, F4, EP>, holds the tile order, the label prefetch and the
+// contraction loop once; EP selects the epilogue: the I store (cc_cosample), the histogram
+// (cc_coassoc) or the item-consensus sums by cluster (cc_item_consensus).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -355,7 +359,7 @@ __device__ unsigned long long cc_co_stamp_acc[8];
   const unsigned long long var = __builtin_amdgcn_s_memtime(); \
   __builtin_amdgcn_sched_barrier(0)
 #define CO_ACC(k, a, b) \
-  if (KP > 1 && threadIdx.x == 0) atomicAdd(&cc_co_stamp_acc[k], (b) - (a))
+  if (EP == EP_HIST && threadIdx.x == 0) atomicAdd(&cc_co_stamp_acc[k], (b) - (a))
 #else
 #define CO_STAMP(var)
 #define CO_ACC(k, a, b)
@@ -571,21 +575,40 @@ __device__ __forceinline__ Acc mfma_step(const v4i& a, const v4i& b, const Acc& 
 __device__ __forceinline__ uint32_t count_of(int v) { return static_cast<uint32_t>(v); }
 __device__ __forceinline__ uint32_t count_of(float v) { return static_cast<uint32_t>(v); }
 
+// One expanded k-chunk of the thread's row (8 one-hot dwords) into its fragment at dst: the two
+// 16-B halves lie 512 B apart (lanes 0-31 and 32-63 of the fragment).
+__device__ __forceinline__ void store_chunk(char* dst, const uint32_t* o) {
+#pragma unroll
+  for (int g = 0; g < 2; ++g)
+    *reinterpret_cast<uint4*>(dst + g * 512) = make_uint4(o[g * 4 + 0], o[g * 4 + 1], o[g * 4 + 2], o[g * 4 + 3]);
+}
+
+// What a workgroup does with its tile's counts after the contraction: store them as uint16
+// co-sampling counts (cc_cosample, KP = 1), bin count / co-sampling count into the histogram
+// (cc_coassoc), or add count / co-sampling count * 2^40 to S by cluster (cc_item_consensus).
+enum { EP_COSAMPLE = 0, EP_HIST = 1, EP_ITEM = 2 };
+
+// The one tile kernel: the loop below runs all three entry points, EP selects the epilogue (the
+// arguments after tile_begin belong to one epilogue each; the others are passed as NULL / 0).
 // F4: the co-association kernels (KP >= 3) contract FP4 one-hot operands, 256 virtual k per
 // super-step (4 chunks of 64): the same LDS bytes and MFMA cycles per step as the i8 form's 128
 // virtual k, so the LDS traffic and the matrix-pipe time per count are halved.  The co-sampling
-// kernel (KP = 1, 0/1 flags of 128 resamples per step) and K <= 2 keep the i8 form.
-template <int KP, bool F4>
+// kernel (KP = 1, 0/1 flags of 128 resamples per step), K <= 2 and the item-consensus kernels
+// (channels padded to a power of two KP >= 2) keep the i8 form.
+template <int KP, bool F4, int EP>
 __global__ __launch_bounds__(NT, 1) void tiles_kernel(
     const uint8_t* __restrict__ labels, int n, int ldl, int Hpad, int64_t tile_begin,
     uint16_t* __restrict__ I_tiles_out, const uint16_t* __restrict__ I_tiles_in,
     const float* __restrict__ edges, unsigned long long* __restrict__ bin_counts,
-    int32_t* __restrict__ full_out, const uint16_t* __restrict__ btab, int bt_rows) {
+    int32_t* __restrict__ full_out, const uint16_t* __restrict__ btab, int bt_rows,
+    const int32_t* __restrict__ cl, int Kc, unsigned long long* __restrict__ S) {
   __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
   constexpr int VK = F4 ? 256 : 128;  // virtual k per super-step
   constexpr int HS = VK / KP;  // resamples per super-step
   constexpr bool EX = (KP & (KP - 1)) != 0;  // exact-K packing (K = KP not a power of two)
   static_assert(!F4 || KP >= 3, "FP4 form: K >= 3");
+  static_assert((EP == EP_COSAMPLE) == (KP == 1), "KP = 1 is the co-sampling kernel");
+  static_assert(EP != EP_ITEM || (!F4 && !EX), "item consensus: i8, power-of-two channels");
   using Acc = std::conditional_t<F4, v16f, v16i>;
 
   CO_STAMP(st0);
@@ -620,7 +643,7 @@ __global__ __launch_bounds__(NT, 1) void tiles_kernel(
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = Acc{};
 
-  // Label prefetch depth: two steps ahead for the co-association kernels (<= 16 label bytes
+  // Label prefetch depth: two steps ahead for every kernel with labels (KP > 1; <= 16 label bytes
   // per row and step); the co-sampling kernel (128 bytes per row and step) loads one step
   // ahead into a single buffer and expands after the MFMAs (its registers would spill).
   constexpr bool PF2 = KP > 1;
@@ -646,10 +669,7 @@ __global__ __launch_bounds__(NT, 1) void tiles_kernel(
     for (int kc = 0; kc < KC; ++kc) {
       uint32_t oc[8];
       expand_kc(kc, oc);
-#pragma unroll
-      for (int g = 0; g < 2; ++g)
-        *reinterpret_cast<uint4*>(wbase + kc * FRAG + g * 512) =
-            make_uint4(oc[g * 4 + 0], oc[g * 4 + 1], oc[g * 4 + 2], oc[g * 4 + 3]);
+      store_chunk(wbase + kc * FRAG, oc);
     }
   };
   if constexpr (EX) {
@@ -666,12 +686,7 @@ __global__ __launch_bounds__(NT, 1) void tiles_kernel(
     load_labels<HS>(rowp, evalid, w);
     expand<KP>(w, o);
 #pragma unroll
-    for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-      for (int g = 0; g < 2; ++g)
-        *reinterpret_cast<uint4*>(wbase + kc * FRAG + g * 512) =
-            make_uint4(o[kc * 8 + g * 4 + 0], o[kc * 8 + g * 4 + 1], o[kc * 8 + g * 4 + 2],
-                       o[kc * 8 + g * 4 + 3]);
+    for (int kc = 0; kc < KC; ++kc) store_chunk(wbase + kc * FRAG, o + kc * 8);
   }
   if constexpr (PF2 && !EX) {
     load_labels<HS>(rowp + (nsteps > 1 ? HS : 0), evalid, w);  // step 1
@@ -720,10 +735,7 @@ __global__ __launch_bounds__(NT, 1) void tiles_kernel(
         // (the stores are unconditional: on the last step they land in the buffer nobody reads)
         uint32_t oc[8];
         expand_kc(kc, oc);
-#pragma unroll
-        for (int g = 0; g < 2; ++g)
-          *reinterpret_cast<uint4*>(wb + kc * FRAG + g * 512) =
-              make_uint4(oc[g * 4 + 0], oc[g * 4 + 1], oc[g * 4 + 2], oc[g * 4 + 3]);
+        store_chunk(wb + kc * FRAG, oc);
         // issue order: each MFMA followed by a few expansion VALU ops, which then execute in
         // that MFMA's 32-cycle shadow instead of after the whole MFMA block
 #pragma unroll
@@ -749,12 +761,7 @@ __global__ __launch_bounds__(NT, 1) void tiles_kernel(
     } else if (more) {
       expand<KP>(w, o);
 #pragma unroll
-      for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-        for (int g = 0; g < 2; ++g)
-          *reinterpret_cast<uint4*>(wb + kc * FRAG + g * 512) =
-              make_uint4(o[kc * 8 + g * 4 + 0], o[kc * 8 + g * 4 + 1], o[kc * 8 + g * 4 + 2],
-                         o[kc * 8 + g * 4 + 3]);
+      for (int kc = 0; kc < KC; ++kc) store_chunk(wb + kc * FRAG, o + kc * 8);
     }
     __syncthreads();
   }
@@ -767,7 +774,7 @@ __global__ __launch_bounds__(NT, 1) void tiles_kernel(
   const int row0 = bi * T + wr * 128 + 4 * (lane >> 5);
   const int col0 = bj * T + wc * 64 + (lane & 31);
 
-  if constexpr (KP == 1) {
+  if constexpr (EP == EP_COSAMPLE) {
     // thread-contiguous tile layout: thread tid's 128 accumulator elements, in (mi, nj, v)
     // order, are elements 128 tid .. 128 tid + 127 (16 x 16-B stores; the co-association
     // epilogue reads them back with 16-B loads)
@@ -801,7 +808,7 @@ __global__ __launch_bounds__(NT, 1) void tiles_kernel(
             }
           }
         }
-  } else {
+  } else if constexpr (EP == EP_HIST) {
     // [NBINS][NT] private counters, the 21 edges, the per-wave sums and (small H) the bin
     // threshold table, reusing the operand LDS.
     uint32_t* hist = reinterpret_cast<uint32_t*>(lds);
@@ -1000,201 +1007,88 @@ __global__ __launch_bounds__(NT, 1) void tiles_kernel(
     }
     CO_STAMP(st5);
     CO_ACC(4, st4, st5);
-  }
-}
-
-// ---- item consensus sums (cc_item_consensus) -------------------------------------------------
-// S[i][c] += sum over j != i with cl[j] == c of C_ij * 2^40, for the pairs of one tile.
-// C_ij = f32(m) / f32(f64(iv) + 1e-6) with 0 <= m <= iv <= 65535 is 0 or a float32 in
-// (2^-17, 1], so C_ij * 2^40 is an integer <= 2^40 and the int64 sums over n <= 2^22 items are
-// exact and order-free (integer atomics): tile ranges, streams and ranks add to the same S.
-//
-// Main loop: the i8 one-hot contraction of tiles_kernel<KP, false> (channels padded to a power
-// of two, labels prefetched two steps ahead, the same 2 x 4 wave arrangement and accumulator
-// order), so the co-sampling counts are read back from I_tiles as the co-association epilogue
-// reads them.  Epilogue: the operand LDS becomes two u64 arrays [256][IC_CB] (row sums by the
-// cluster of the column, column sums by the cluster of the row; rows padded to IC_CS entries so
-// that the 32 columns of a wave's half land on different banks), filled with 64-bit LDS atomics
-// and flushed with one 64-bit global atomic per non-zero entry, IC_CB clusters per pass with the
-// accumulators kept in registers.  An off-diagonal tile (bi < bj) holds each pair once and adds
-// it to both sides; a diagonal tile holds the full block and adds row sums only.
-constexpr int IC_CB = 16;          // clusters per pass
-constexpr int IC_CS = IC_CB + 1;   // padded row of the LDS sums (u64 entries)
-constexpr int IC_LDS = 2 * T * IC_CS * 8 + 2 * T * 4;
-static_assert(IC_LDS <= LDS_BYTES, "the sums and the staged clusters reuse the operand LDS");
-
-template <int KP>
-__global__ __launch_bounds__(NT, 1) void item_consensus_kernel(
-    const uint8_t* __restrict__ labels, int n, int ldl, int Hpad, int64_t tile_begin,
-    const uint16_t* __restrict__ I_tiles_in, const int32_t* __restrict__ cl, int Kc,
-    unsigned long long* __restrict__ S) {
-  __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
-  static_assert(KP >= 2 && KP <= 128 && (KP & (KP - 1)) == 0, "power-of-two channels");
-  constexpr int HS = 128 / KP;  // resamples per super-step
-  constexpr int NWD = (HS + 3) / 4;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wr = wave >> 2;  // 0..1 : 128-row half
-  const int wc = wave & 3;   // 0..3 : 64-col quarter
-  const int nb = (n + T - 1) / T;
-  // the tile order of tiles_kernel (contiguous tile ranges per XCD)
-  const int nblk = static_cast<int>(gridDim.x), bx = static_cast<int>(blockIdx.x);
-  const int xq = nblk >> 3, xr = nblk & 7, xcd = bx & 7;
-  const int64_t t = tile_begin + xcd * xq + (xcd < xr ? xcd : xr) + (bx >> 3);
-  int bi, bj;
-  tile_coords(t, nb, bi, bj);
-
-  // Expansion role: one row per thread. side 0 = tile rows (A), side 1 = tile cols (B).
-  const int side = tid >> 8;
-  const int erow = tid & 255;
-  const int grow = (side ? bj : bi) * T + erow;
-  const bool evalid = grow < n;
-  const uint8_t* rowp = labels + static_cast<int64_t>(evalid ? grow : 0) * ldl;
-  const int erb = erow >> 5, er = erow & 31;
-  char* const wbase = lds + side * SIDE + erb * KC * FRAG + er * 16;
-
-  const int nsteps = Hpad / HS;
-  v16i acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = v16i{};
-
-  uint32_t w[32], wn[NWD];
-  load_labels<HS>(rowp, evalid, w);
-#pragma unroll
-  for (int kc = 0; kc < KC; ++kc) {  // step 0's one-hot straight into LDS buffer 0
-    uint32_t oc[8];
-    expand_chunk<KP>(w, kc, oc);
-#pragma unroll
-    for (int g = 0; g < 2; ++g)
-      *reinterpret_cast<uint4*>(wbase + kc * FRAG + g * 512) =
-          make_uint4(oc[g * 4 + 0], oc[g * 4 + 1], oc[g * 4 + 2], oc[g * 4 + 3]);
-  }
-  load_labels<HS>(rowp + (nsteps > 1 ? HS : 0), evalid, w);  // step 1
-  {
-    uint32_t t32[32];
-    load_labels<HS>(rowp + (nsteps > 2 ? 2 * HS : 0), evalid, t32);  // step 2
-#pragma unroll
-    for (int q = 0; q < NWD; ++q) wn[q] = t32[q];
-  }
-  __syncthreads();
-
-  for (int s = 0; s < nsteps; ++s) {
-    const char* rb = lds + (s & 1) * BUF;
-    char* wb = wbase + ((s + 1) & 1) * BUF;
-    v4i a[2][4], b[2][2];
-    auto frags = [&](int kc, v4i (&fa)[4], v4i (&fb)[2]) __attribute__((always_inline)) {
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-        fa[mi] = *reinterpret_cast<const v4i*>(rb + ((wr * 4 + mi) * KC + kc) * FRAG + lane * 16);
-#pragma unroll
-      for (int nj = 0; nj < 2; ++nj)
-        fb[nj] = *reinterpret_cast<const v4i*>(rb + SIDE + ((wc * 2 + nj) * KC + kc) * FRAG +
-                                               lane * 16);
-    };
-    frags(0, a[0], b[0]);
-#pragma unroll
-    for (int kc = 0; kc < KC; ++kc) {
-      const int cb = kc & 1;
-      if (kc + 1 < KC) frags(kc + 1, a[cb ^ 1], b[cb ^ 1]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int nj = 0; nj < 2; ++nj)
-          acc[mi][nj] = mfma_step<false>(a[cb][mi], b[cb][nj], acc[mi][nj]);
-      // step s+1's one-hot, chunk by chunk in the MFMA shadows (on the last step the stores
-      // land in the buffer nobody reads)
-      uint32_t oc[8];
-      expand_chunk<KP>(w, kc, oc);
-#pragma unroll
-      for (int g = 0; g < 2; ++g)
-        *reinterpret_cast<uint4*>(wb + kc * FRAG + g * 512) =
-            make_uint4(oc[g * 4 + 0], oc[g * 4 + 1], oc[g * 4 + 2], oc[g * 4 + 3]);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
-        __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);  // VALU per MFMA
-      }
-      __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);    // the 2 LDS stores
+  } else {
+    // ---- item consensus sums (cc_item_consensus) ---------------------------------------------
+    // S[i][c] += sum over j != i with cl[j] == c of C_ij * 2^40, for the pairs of one tile.
+    // C_ij = f32(m) / f32(f64(iv) + 1e-6) with 0 <= m <= iv <= 65535 is 0 or a float32 in
+    // (2^-17, 1], so C_ij * 2^40 is an integer <= 2^40 and the int64 sums over n <= 2^22 items
+    // are exact and order-free (integer atomics): tile ranges, streams, ranks add to one S.
+    //
+    // The accumulators are in the order of the co-association kernels, so the co-sampling
+    // counts are read back from I_tiles as the histogram epilogue reads them.  The operand LDS
+    // (free after the loop's last barrier) becomes two u64 arrays [256][IC_CB] (row sums by the
+    // cluster of the column, column sums by the cluster of the row; rows padded to IC_CS
+    // entries so that the 32 columns of a wave's half land on different banks), filled with
+    // 64-bit LDS atomics and flushed with one 64-bit global atomic per non-zero entry, IC_CB
+    // clusters per pass with the accumulators kept in registers.  An off-diagonal tile
+    // (bi < bj) holds each pair once and adds it to both sides; a diagonal tile holds the full
+    // block and adds row sums only.
+    constexpr int IC_CB = 16;          // clusters per pass
+    constexpr int IC_CS = IC_CB + 1;   // padded row of the LDS sums (u64 entries)
+    constexpr int IC_LDS = 2 * T * IC_CS * 8 + 2 * T * 4;
+    static_assert(IC_LDS <= LDS_BYTES, "the sums and the staged clusters reuse the operand LDS");
+    unsigned long long* rsum = reinterpret_cast<unsigned long long*>(lds);  // [T][IC_CS] by row
+    unsigned long long* csum = rsum + T * IC_CS;                            // [T][IC_CS] by column
+    int* clr = reinterpret_cast<int*>(csum + T * IC_CS);                    // clusters of the rows
+    int* clc = clr + T;                                                     // ... of the columns
+    {
+      // an id outside [0, Kc) = no cluster: -1, which no pass matches
+      const int v = evalid ? cl[grow] : -1;
+      (side ? clc : clr)[erow] = (v >= 0 && v < Kc) ? v : -1;
     }
-    // rotate the label prefetch: w <- step s+2, wn <- step s+3 (clamped re-reads at the end)
-#pragma unroll
-    for (int q = 0; q < NWD; ++q) w[q] = wn[q];
-    uint32_t t32[32];
-    load_labels<HS>(rowp + ((s + 3) < nsteps ? s + 3 : s) * HS, evalid, t32);
-#pragma unroll
-    for (int q = 0; q < NWD; ++q) wn[q] = t32[q];
-    __syncthreads();
-  }
+    const int rl0 = wr * 128 + 4 * (lane >> 5);  // tile-local row and column of element (0, 0, 0)
+    const int cl0 = wc * 64 + (lane & 31);
+    const uint4* it4 = reinterpret_cast<const uint4*>(I_tiles_in + tl * (T * T) + 128 * tid);
 
-  // ---- epilogue: the operand LDS is free after the loop's last barrier ----------------------
-  const int64_t tl = t - tile_begin;
-  const bool diag = (bi == bj);
-  unsigned long long* rsum = reinterpret_cast<unsigned long long*>(lds);  // [T][IC_CS] by row
-  unsigned long long* csum = rsum + T * IC_CS;                            // [T][IC_CS] by column
-  int* clr = reinterpret_cast<int*>(csum + T * IC_CS);                    // clusters of the rows
-  int* clc = clr + T;                                                     // ... of the columns
-  {
-    // an id outside [0, Kc) = no cluster: -1, which no pass matches
-    const int v = evalid ? cl[grow] : -1;
-    (side ? clc : clr)[erow] = (v >= 0 && v < Kc) ? v : -1;
-  }
-  const int rl0 = wr * 128 + 4 * (lane >> 5);  // tile-local row and column of element (0, 0, 0)
-  const int cl0 = wc * 64 + (lane & 31);
-  const uint4* it4 = reinterpret_cast<const uint4*>(I_tiles_in + tl * (T * T) + 128 * tid);
-
-  for (int c0 = 0; c0 < Kc; c0 += IC_CB) {
-    for (int e = tid; e < 2 * T * IC_CS; e += NT) rsum[e] = 0ull;
-    __syncthreads();  // (first pass: the staged clusters too)
-    // opaque per pass: the 128 pair masks and LDS addresses and the tile's 64 co-sampling
-    // dwords would otherwise be hoisted out of the pass loop and spill next to the 128
-    // accumulators
-    int rl = rl0, cc0 = cl0;
-    int zero = 0;
-    asm volatile("" : "+v"(rl), "+v"(cc0), "+v"(zero));
-    const uint4* itp = it4 + zero;
+    for (int c0 = 0; c0 < Kc; c0 += IC_CB) {
+      for (int e = tid; e < 2 * T * IC_CS; e += NT) rsum[e] = 0ull;
+      __syncthreads();  // (first pass: the staged clusters too)
+      // opaque per pass: the 128 pair masks and LDS addresses and the tile's 64 co-sampling
+      // dwords would otherwise be hoisted out of the pass loop and spill next to the 128
+      // accumulators
+      int rl = rl0, cc0 = cl0;
+      int zero = 0;
+      asm volatile("" : "+v"(rl), "+v"(cc0), "+v"(zero));
+      const uint4* itp = it4 + zero;
 #pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
+      for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-      for (int nj = 0; nj < 2; ++nj) {
-        asm volatile("" : "+v"(acc[mi][nj]));  // (nor the 128 fixed-point values)
-        const uint4 q0 = itp[(mi * 2 + nj) * 2], q1 = itp[(mi * 2 + nj) * 2 + 1];
-        const uint32_t iw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-        const int jl = cc0 + nj * 32;
-        const int j = bj * T + jl;
-        const uint32_t cj = static_cast<uint32_t>(clc[jl] - c0);  // column's cluster in this pass
+        for (int nj = 0; nj < 2; ++nj) {
+          asm volatile("" : "+v"(acc[mi][nj]));  // (nor the 128 fixed-point values)
+          const uint4 q0 = itp[(mi * 2 + nj) * 2], q1 = itp[(mi * 2 + nj) * 2 + 1];
+          const uint32_t iw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+          const int jl = cc0 + nj * 32;
+          const int j = bj * T + jl;
+          const uint32_t cj = static_cast<uint32_t>(clc[jl] - c0);  // column's cluster in this pass
 #pragma unroll
-        for (int v = 0; v < 16; ++v) {
-          const uint32_t iv = (iw[v >> 1] >> (16 * (v & 1))) & 0xFFFFu;
-          const uint32_t m = static_cast<uint32_t>(acc[mi][nj][v]);
-          const int il = rl + mi * 32 + (v & 3) + 8 * (v >> 2);
-          const int i = bi * T + il;
-          if (m != 0 && i < n && j < n && i != j) {  // m == 0: C_ij = 0 adds nothing
-            const float fi = static_cast<float>(static_cast<double>(iv) + 1e-6);
-            const float x = static_cast<float>(m) / fi;  // IEEE RN, as consensus_bin
-            const unsigned long long q =
-                static_cast<unsigned long long>(static_cast<long long>(static_cast<double>(x) * 1099511627776.0));
-            if (cj < static_cast<uint32_t>(IC_CB)) atomicAdd(&rsum[il * IC_CS + cj], q);
-            if (!diag) {
-              const uint32_t ci = static_cast<uint32_t>(clr[il] - c0);
-              if (ci < static_cast<uint32_t>(IC_CB)) atomicAdd(&csum[jl * IC_CS + ci], q);
+          for (int v = 0; v < 16; ++v) {
+            const uint32_t iv = (iw[v >> 1] >> (16 * (v & 1))) & 0xFFFFu;
+            const uint32_t m = static_cast<uint32_t>(acc[mi][nj][v]);
+            const int il = rl + mi * 32 + (v & 3) + 8 * (v >> 2);
+            const int i = bi * T + il;
+            if (m != 0 && i < n && j < n && i != j) {  // m == 0: C_ij = 0 adds nothing
+              const float fi = static_cast<float>(static_cast<double>(iv) + 1e-6);
+              const float x = static_cast<float>(m) / fi;  // IEEE RN, as consensus_bin
+              const unsigned long long q =
+                  static_cast<unsigned long long>(static_cast<long long>(static_cast<double>(x) * 1099511627776.0));
+              if (cj < static_cast<uint32_t>(IC_CB)) atomicAdd(&rsum[il * IC_CS + cj], q);
+              if (!diag) {
+                const uint32_t ci = static_cast<uint32_t>(clr[il] - c0);
+                if (ci < static_cast<uint32_t>(IC_CB)) atomicAdd(&csum[jl * IC_CS + ci], q);
+              }
             }
           }
         }
+      __syncthreads();
+      for (int e = tid; e < 2 * T * IC_CB; e += NT) {
+        const int sd = e / (T * IC_CB), r = (e / IC_CB) % T, c = e % IC_CB;
+        const unsigned long long val = (sd ? csum : rsum)[r * IC_CS + c];
+        const int g = (sd ? bj : bi) * T + r;
+        if (val != 0ull && g < n && c0 + c < Kc)
+          atomicAdd(&S[static_cast<int64_t>(g) * Kc + c0 + c], val);
       }
-    __syncthreads();
-    for (int e = tid; e < 2 * T * IC_CB; e += NT) {
-      const int sd = e / (T * IC_CB), r = (e / IC_CB) % T, c = e % IC_CB;
-      const unsigned long long val = (sd ? csum : rsum)[r * IC_CS + c];
-      const int g = (sd ? bj : bi) * T + r;
-      if (val != 0ull && g < n && c0 + c < Kc)
-        atomicAdd(&S[static_cast<int64_t>(g) * Kc + c0 + c], val);
+      __syncthreads();  // the next pass clears the sums
     }
-    __syncthreads();  // the next pass clears the sums
   }
 }
 
@@ -1312,13 +1206,42 @@ int launch_status(const char* fn) {
   return CC_OK;
 }
 
-template <int KP, bool F4 = false>
-void launch_tiles(dim3 grid, hipStream_t st, const uint8_t* lab, int n, int ldl, int Hpad,
-                  int64_t tb, uint16_t* Iout, const uint16_t* Iin, const float* edges,
-                  unsigned long long* counts, int32_t* full, const uint16_t* btab = nullptr,
-                  int bt_rows = 0) {
-  hipLaunchKernelGGL((tiles_kernel<KP, F4>), grid, dim3(NT), 0, st, lab, n, ldl, Hpad, tb, Iout, Iin,
-                     edges, counts, full, btab, bt_rows);
+// One launch of tiles_kernel over [tb, tb + ntl): what cc_cosample, cc_coassoc and
+// cc_item_consensus share.  ntl == 0 is an empty band (a rank with no tiles): nothing to launch.
+struct TileLaunch {
+  const uint8_t* lab;
+  int n, ldl, Hpad;
+  int64_t tb, ntl;
+  hipStream_t st;
+};
+
+// The prelude of the three: check_common, the entry point's own range check (range_err: its
+// message, or NULL), the empty band and the one-launch limit.  Not CC_OK: refused, the error is
+// set.  CC_OK with tl.ntl == 0: done, nothing to launch.  The pointer checks of each entry point
+// come after it: an empty band may pass NULL buffers.
+int tile_prelude(const char* fn, const char* range_err, const int8_t* labels_nh, int n, int ldl, int Hpad,
+                 int64_t tb, int64_t te, void* stream, TileLaunch& tl) {
+  int rc = check_common(fn, labels_nh, n, ldl, Hpad, tb, te);
+  if (rc) return rc;
+  if (range_err) {
+    cc::set_error(std::string(fn) + ": " + range_err);
+    return CC_ERR_ARG;
+  }
+  tl = TileLaunch{reinterpret_cast<const uint8_t*>(labels_nh), n, ldl, Hpad, tb, te - tb,
+                  static_cast<hipStream_t>(stream)};
+  if (tl.ntl > 0x7fffffff) {
+    cc::set_error(std::string(fn) + ": too many tiles for one launch");
+    return CC_ERR_ARG;
+  }
+  return CC_OK;
+}
+
+template <int KP, bool F4, int EP>
+void launch_tiles(const TileLaunch& tl, uint16_t* Iout, const uint16_t* Iin, const float* edges,
+                  unsigned long long* counts, int32_t* full, const uint16_t* btab, int bt_rows,
+                  const int32_t* cl, int Kc, unsigned long long* S) {
+  hipLaunchKernelGGL((tiles_kernel<KP, F4, EP>), dim3(static_cast<unsigned>(tl.ntl)), dim3(NT), 0, tl.st, tl.lab,
+                     tl.n, tl.ldl, tl.Hpad, tl.tb, Iout, Iin, edges, counts, full, btab, bt_rows, cl, Kc, S);
 }
 
 }  // namespace
@@ -1361,22 +1284,14 @@ extern "C" int cc_copy_label_columns(const uint8_t* src, int64_t ld_src, int col
 
 extern "C" int cc_cosample(const int8_t* labels_nh, int n, int ldl, int Hpad, int64_t tile_begin,
                            int64_t tile_end, uint16_t* I_tiles, int32_t* I_full, void* stream) {
-  int rc = check_common("cc_cosample", labels_nh, n, ldl, Hpad, tile_begin, tile_end);
-  if (rc) return rc;
-  if (tile_end == tile_begin) return CC_OK;  // an empty band (a rank with no tiles)
+  TileLaunch tl;
+  int rc = tile_prelude("cc_cosample", nullptr, labels_nh, n, ldl, Hpad, tile_begin, tile_end, stream, tl);
+  if (rc || tl.ntl == 0) return rc;
   if (!I_tiles || (reinterpret_cast<uintptr_t>(I_tiles) & 15)) {
     cc::set_error("cc_cosample: I_tiles is NULL or not 16-B aligned");
     return CC_ERR_ARG;
   }
-  const int64_t ntl = tile_end - tile_begin;
-  if (ntl == 0) return CC_OK;
-  if (ntl > 0x7fffffff) {
-    cc::set_error("cc_cosample: too many tiles for one launch");
-    return CC_ERR_ARG;
-  }
-  launch_tiles<1>(dim3(static_cast<unsigned>(ntl)), static_cast<hipStream_t>(stream),
-                  reinterpret_cast<const uint8_t*>(labels_nh), n, ldl, Hpad, tile_begin, I_tiles,
-                  nullptr, nullptr, nullptr, I_full);
+  launch_tiles<1, false, EP_COSAMPLE>(tl, I_tiles, nullptr, nullptr, nullptr, I_full, nullptr, 0, nullptr, 0, nullptr);
   return launch_status("cc_cosample");
 }
 
@@ -1424,13 +1339,10 @@ extern "C" int cc_coassoc(const int8_t* labels_nh, int n, int ldl, int Hpad, int
                           int64_t tile_begin, int64_t tile_end, const uint16_t* I_tiles,
                           const float* edges, unsigned long long* bin_counts, int32_t* M_full,
                           const uint16_t* bin_table, int table_rows, void* stream) {
-  int rc = check_common("cc_coassoc", labels_nh, n, ldl, Hpad, tile_begin, tile_end);
-  if (rc) return rc;
-  if (K < 1 || K > 127) {
-    cc::set_error("cc_coassoc: K must be in [1, 127]");
-    return CC_ERR_ARG;
-  }
-  if (tile_end == tile_begin) return CC_OK;  // an empty band (a rank with no tiles)
+  TileLaunch tl;
+  int rc = tile_prelude("cc_coassoc", (K < 1 || K > 127) ? "K must be in [1, 127]" : nullptr, labels_nh, n, ldl, Hpad,
+                        tile_begin, tile_end, stream, tl);
+  if (rc || tl.ntl == 0) return rc;
   if (!I_tiles || !edges || !bin_counts) {
     cc::set_error("cc_coassoc: I_tiles, edges and bin_counts are required");
     return CC_ERR_ARG;
@@ -1443,15 +1355,6 @@ extern "C" int cc_coassoc(const int8_t* labels_nh, int n, int ldl, int Hpad, int
     cc::set_error("cc_coassoc: bin_table needs Hpad + 1 <= table_rows <= cc_bin_table_max_rows()");
     return CC_ERR_ARG;
   }
-  const int64_t ntl = tile_end - tile_begin;
-  if (ntl == 0) return CC_OK;
-  if (ntl > 0x7fffffff) {
-    cc::set_error("cc_coassoc: too many tiles for one launch");
-    return CC_ERR_ARG;
-  }
-  const dim3 grid(static_cast<unsigned>(ntl));
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const uint8_t* lab = reinterpret_cast<const uint8_t*>(labels_nh);
   // K <= 2: i8 one-hot (KP = 2, 64 resamples per step).  K >= 3: FP4 one-hot, 256 virtual k
   // per step, channels padded to the next power of two KP >= 4, or exact-K packing (ExactK) for
   // K = 17, 18, where it saves over 40 % of the super-steps.  Measured at C3
@@ -1468,11 +1371,11 @@ extern "C" int cc_coassoc(const int8_t* labels_nh, int n, int ldl, int Hpad, int
     if (force_exact || (!force_pow2 && 5 * se <= 3 * sp)) kp = K;
   }
   switch (kp) {
-#define CC_F4(k) case k: launch_tiles<k, true>(grid, st, lab, n, ldl, Hpad, tile_begin, nullptr, I_tiles, edges, bin_counts, M_full, bin_table, table_rows); break;
-    CC_F4(4) CC_F4(8) CC_F4(16) CC_F4(17) CC_F4(18) CC_F4(32) CC_F4(64)
-#undef CC_F4
-    case 2: launch_tiles<2>(grid, st, lab, n, ldl, Hpad, tile_begin, nullptr, I_tiles, edges, bin_counts, M_full, bin_table, table_rows); break;
-    default: launch_tiles<128, true>(grid, st, lab, n, ldl, Hpad, tile_begin, nullptr, I_tiles, edges, bin_counts, M_full, bin_table, table_rows); break;
+#define CC_CO(k, f4) case k: launch_tiles<k, f4, EP_HIST>(tl, nullptr, I_tiles, edges, bin_counts, M_full, bin_table, table_rows, nullptr, 0, nullptr); break;
+    CC_CO(2, false) CC_CO(4, true) CC_CO(8, true) CC_CO(16, true) CC_CO(17, true) CC_CO(18, true) CC_CO(32, true)
+    CC_CO(64, true)
+    default: CC_CO(128, true)
+#undef CC_CO
   }
   return launch_status("cc_coassoc");
 }
@@ -1480,17 +1383,11 @@ extern "C" int cc_coassoc(const int8_t* labels_nh, int n, int ldl, int Hpad, int
 extern "C" int cc_item_consensus(const int8_t* labels_nh, int n, int ldl, int Hpad, int K,
                                  int64_t tile_begin, int64_t tile_end, const uint16_t* I_tiles,
                                  const int32_t* cl, int Kc, int64_t* S, void* stream) {
-  int rc = check_common("cc_item_consensus", labels_nh, n, ldl, Hpad, tile_begin, tile_end);
-  if (rc) return rc;
-  if (K < 1 || K > 127 || Kc < 1 || Kc > 127) {
-    cc::set_error("cc_item_consensus: K and Kc must be in [1, 127]");
-    return CC_ERR_ARG;
-  }
-  if (n > (1 << 22)) {
-    cc::set_error("cc_item_consensus: n > 2^22 (the 2^40 fixed-point row sums must fit int64)");
-    return CC_ERR_ARG;
-  }
-  if (tile_end == tile_begin) return CC_OK;  // an empty band (a rank with no tiles)
+  const char* range_err = (K < 1 || K > 127 || Kc < 1 || Kc > 127) ? "K and Kc must be in [1, 127]"
+                          : n > (1 << 22) ? "n > 2^22 (the 2^40 fixed-point row sums must fit int64)" : nullptr;
+  TileLaunch tl;
+  int rc = tile_prelude("cc_item_consensus", range_err, labels_nh, n, ldl, Hpad, tile_begin, tile_end, stream, tl);
+  if (rc || tl.ntl == 0) return rc;
   if (!cl || !S || !I_tiles) {
     cc::set_error("cc_item_consensus: I_tiles, cl and S are required");
     return CC_ERR_ARG;
@@ -1500,19 +1397,11 @@ extern "C" int cc_item_consensus(const int8_t* labels_nh, int n, int ldl, int Hp
     cc::set_error("cc_item_consensus: S must be 8-B aligned (64-bit atomics), cl 4-B, I_tiles 16-B");
     return CC_ERR_ARG;
   }
-  const int64_t ntl = tile_end - tile_begin;
-  if (ntl > 0x7fffffff) {
-    cc::set_error("cc_item_consensus: too many tiles for one launch");
-    return CC_ERR_ARG;
-  }
-  const dim3 grid(static_cast<unsigned>(ntl));
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const uint8_t* lab = reinterpret_cast<const uint8_t*>(labels_nh);
   unsigned long long* Su = reinterpret_cast<unsigned long long*>(S);
   int kp = 2;  // channels padded to the next power of two (K = 1 runs as KP = 2)
   while (kp < K) kp <<= 1;
   switch (kp) {
-#define CC_IC(k) case k: hipLaunchKernelGGL((item_consensus_kernel<k>), grid, dim3(NT), 0, st, lab, n, ldl, Hpad, tile_begin, I_tiles, cl, Kc, Su); break;
+#define CC_IC(k) case k: launch_tiles<k, false, EP_ITEM>(tl, nullptr, I_tiles, nullptr, nullptr, nullptr, nullptr, 0, cl, Kc, Su); break;
     CC_IC(2) CC_IC(4) CC_IC(8) CC_IC(16) CC_IC(32) CC_IC(64)
     default: CC_IC(128)
 #undef CC_IC

@@ -91,6 +91,12 @@ CASES = [
     (260, 5, 0.3, 4, 3),       # pairs never co-sampled and items never sampled
     (1, 5, 1.0, 2, 2),
     (2, 5, 1.0, 2, 2),
+    # the channel widths the cases above do not reach (KP = 16, 32, 64) and K = 1 (runs as KP = 2),
+    # at the smallest n with a diagonal tile, an off-diagonal tile and a one-row ragged block
+    (257, 37, 0.6, 9, 3),
+    (257, 37, 0.6, 17, 3),
+    (257, 37, 0.6, 33, 3),
+    (257, 5, 1.0, 1, 2),
 ]
 
 

@@ -17,12 +17,13 @@ for P in "$P1" "$P2" "$P3"; do
   timeout -s KILL 120 rocprofv3 --pmc $P -d $OUT/p$i -o p$i --output-format csv -- python3 $GRAFT_REPO_ROOT/tools/co_only.py ${CO_CFG:-c3} ${CO_K:-20} > $OUT/p$i.log 2>&1 || { echo "pass $i failed"; tail -5 $OUT/p$i.log; exit 1; }
 done
 python3 - <<'PY'
-import collections, csv, glob, os
+import collections, csv, glob, os, re
 root = os.environ["GRAFT_REPO_ROOT"] + "/gpurun_out/co"
 v = collections.defaultdict(float)
 for f in glob.glob(root + "/p*/p*_counter_collection.csv"):
     for r in csv.DictReader(open(f)):
-        if "tiles_kernel" in r["Kernel_Name"] and "<1>" not in r["Kernel_Name"]:
+        # the co-association instantiations: tiles_kernel<KP, F4, 1> (the histogram epilogue)
+        if re.search(r"tiles_kernel<\d+, (?:true|false), 1>", r["Kernel_Name"]):
             v[r["Counter_Name"]] += float(r["Counter_Value"])
 w = v["SQ_WAVES"]
 print({k: round(x / w) for k, x in sorted(v.items())})

@@ -2,6 +2,7 @@
 # by tools/sq_summary.py: MFMA busy as a % of SIMD cycles, VALU/MFMA, wait split, LDS conflicts.
 #   SQ_TAG=km_c3 SQ_FILTER=kmeans_kernel bash tools/gpu_sq.sh tools/km_only.py 1000 c3
 #   SQ_TAG=co_c3 SQ_FILTER=tiles_kernel  bash tools/gpu_sq.sh tools/co_only.py c3
+# (tiles_kernel<KP, F4, EP> runs cc_cosample, cc_coassoc and cc_item_consensus: EP = 0, 1, 2)
 set -o pipefail
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/sq_${SQ_TAG:-run}

@@ -4,7 +4,10 @@
 (c) at n = 20 000: the materialised route (cosample full, coassoc full, consensus, * 2^40,
     index_add by cluster) against item_consensus_sums.
 
-    python tools/icl_time.py [output.txt]      (profiles/icl/icl_timing.txt is one run's output)"""
+    python tools/icl_time.py [output.txt [K [kernel]]]
+                                               (profiles/icl/icl_timing.txt is one run's output)
+K (default 8) is the number of label values of (a), (b) and (c); with a third argument "kernel"
+only line (a'), the cc_item_consensus launch alone, is timed (an A/B of two libraries)."""
 import os
 import statistics
 import sys
@@ -62,18 +65,20 @@ def make(n, H, K, Kc, frac=0.8, seed=0):
 say("device", torch.cuda.get_device_name(0), "runs", RUNS, "warm-up", WARM)
 
 # (a), (b): the C3 shape
-n, H, K, Kc = 50000, 1000, 8, 8
+n, H, K, Kc = 50000, 1000, int(sys.argv[2]) if len(sys.argv) > 2 else 8, 8
+KERNEL_ONLY = len(sys.argv) > 3 and sys.argv[3] == "kernel"
 L, Hpad, cl = make(n, H, K, Kc)
 nt = engine.num_tiles(n)
 say(f"shape n={n} H={H} Hpad={Hpad} K={K} Kc={Kc} tiles={nt}")
-a_ms = report("(a) item_consensus_sums, tile_chunk 2048 (cosample + item kernel per chunk)",
-              timed_ms(lambda: engine.item_consensus_sums(L, n, Hpad, K, cl, Kc)))
-engine.TIMERS = {}
-engine.item_consensus_sums(L, n, Hpad, K, cl, Kc)
-torch.cuda.synchronize()
-for k, (cnt, ms) in engine.timer_summary(engine.TIMERS).items():
-    say(f"    one call, per kernel: {k}: {cnt} launches, {ms:.3f} ms")
-engine.TIMERS = None
+if not KERNEL_ONLY:
+    a_ms = report("(a) item_consensus_sums, tile_chunk 2048 (cosample + item kernel per chunk)",
+                  timed_ms(lambda: engine.item_consensus_sums(L, n, Hpad, K, cl, Kc)))
+    engine.TIMERS = {}
+    engine.item_consensus_sums(L, n, Hpad, K, cl, Kc)
+    torch.cuda.synchronize()
+    for k, (cnt, ms) in engine.timer_summary(engine.TIMERS).items():
+        say(f"    one call, per kernel: {k}: {cnt} launches, {ms:.3f} ms")
+    engine.TIMERS = None
 
 I_tiles, _ = engine.cosample(L, n, Hpad, 0, nt)
 S = torch.zeros((n, Kc), dtype=torch.int64, device=dev)
@@ -83,9 +88,11 @@ a1_ms = report("(a') cc_item_consensus alone, one launch over all tiles (co-samp
                                                  I_tiles.data_ptr(), cl.data_ptr(), Kc, S.data_ptr(),
                                                  engine.stream_ptr())))
 assert bool((S == (WARM + RUNS) * S_chunked).all()), "one launch and the chunked walk disagree"
+if KERNEL_ONLY:
+    sys.exit(0)
 edges = engine.edges_device(dev)
 counts = torch.zeros(20, dtype=torch.int64, device=dev)
-b_ms = report("(b) cc_coassoc K=8, one launch over all tiles (FP4 contraction + histogram)",
+b_ms = report(f"(b) cc_coassoc K={K}, one launch over all tiles (FP4 contraction + histogram)",
               timed_ms(lambda: engine.coassoc(L, n, Hpad, K, 0, nt, I_tiles, edges, counts)))
 c_ms = report("    cc_cosample, one launch over all tiles", timed_ms(lambda: engine.cosample(L, n, Hpad, 0, nt)))
 say(f"ratios: (a)/(b) = {a_ms / b_ms:.2f}  (a')/(b) = {a1_ms / b_ms:.2f}")

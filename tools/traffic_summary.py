@@ -11,14 +11,23 @@ import csv
 import glob
 import json
 import os
+import re
 import sys
 
 root, config, tag = sys.argv[1], sys.argv[2], sys.argv[3]
-# tiles_kernel<1, false> is the co-sampling instantiation (demangled names carry every template
-# argument)
+
+
+# One tile kernel runs three entry points: the last template argument of tiles_kernel<KP, F4, EP>
+# is the epilogue, an int (EP_COSAMPLE = 0, EP_HIST = 1, EP_ITEM = 2 in csrc/coassoc.hip); demangled
+# names carry every template argument, e.g. "tiles_kernel<8, true, 1>".
+def tile_epilogue(ep):
+    return lambda k: re.search(r"tiles_kernel<\d+, (?:true|false), %d>" % ep, k) is not None
+
+
 KERNELS = {"cc_kmeans_batched": lambda k: "kmeans_kernel" in k,
-           "cc_coassoc": lambda k: "tiles_kernel" in k and "tiles_kernel<1," not in k,
-           "cc_cosample": lambda k: "tiles_kernel<1," in k}
+           "cc_cosample": tile_epilogue(0),
+           "cc_coassoc": tile_epilogue(1),
+           "cc_item_consensus": tile_epilogue(2)}
 tot = collections.defaultdict(float)
 disp = collections.defaultdict(set)
 for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
