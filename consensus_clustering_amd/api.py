@@ -21,7 +21,10 @@ What runs where (``fit``):
                   (e.g. GaussianMixture) keeps the reference's host fit_predict per
                   (K, h) and only its labels go to the GPU (hybrid path); PAM (pam.py, k-medoids
                   under the same four metrics) -> BUILD and SWAP of every (resample, K) on the
-                  device over the same distances (cc_pam_build, cc_pam_swap_step, cc_pam_labels)
+                  device over the same distances (cc_pam_build, cc_pam_swap_step, cc_pam_labels);
+                  GMM (gmm.py, sklearn's diagonal Gaussian mixture in float64) -> batched EM of
+                  every (resample, K), each init started from the float64 k-means engine's labels
+                  (cc_gmm_gather, cc_gmm_start, cc_gmm_em_step, cc_gmm_finish)
   I, M, histogram int8-MFMA tiles of the upper triangle (cc_cosample / cc_coassoc)
   hist/cdf/PAC    host float64 from 20 exact integer counts (post.py)
   multi-GPU       resamples and triangle tiles sharded over torch.distributed ranks
@@ -53,6 +56,7 @@ from .kmeans import BatchedKMeans
 from .pam import METRICS as HC_METRICS  # sklearn's metric spellings -> scipy's names
 from .pam import PAM, degenerate_rows as _hc_degenerate, refuse_not_finite
 from .pam import validate as _pam_validate
+from .gmm import GMM, validate as _gmm_validate
 
 KMAX = 127  # largest K: uint8 labels (0xFF = not sampled) and int8 one-hot channels
 
@@ -218,6 +222,29 @@ def _pam_route(metric, X):
     return metric
 
 
+def _gmm_spec(est):
+    """The parameters of a GMM that the device reproduces (cc_gmm_start, cc_gmm_em_step,
+    cc_gmm_finish), else None: exactly that type (a subclass may override anything), diagonal
+    covariances, integer max_iter >= 1 and n_init >= 1, finite tol >= 0 and reg_covar >= 0."""
+    if type(est) is not GMM:
+        return None
+    p = est.get_params()
+    if not isinstance(p.get("covariance_type"), str) or p["covariance_type"] != 'diag':
+        return None
+    for name in ("max_iter", "n_init"):
+        v = p.get(name)
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+            return None
+    for name in ("tol", "reg_covar"):
+        v = p.get(name)
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            return None
+        if not (np.isfinite(v) and v >= 0):
+            return None
+    return dict(n_init=int(p["n_init"]), max_iter=int(p["max_iter"]), tol=float(p["tol"]),
+                reg_covar=float(p["reg_covar"]))
+
+
 class ConsensusClustering:
     """Monti consensus clustering on MI355X.  Drop-in for CC.py:11."""
 
@@ -357,6 +384,7 @@ class ConsensusClustering:
         self.kmeans_inertia_ = self.kmeans_n_iter_ = self.kmeans_stats_ = None
         self.hc_stats_ = self.hc_metric_ = None
         self.pam_stats_ = self.pam_metric_ = self.pam_inertia_ = self.pam_n_iter_ = None
+        self.gmm_stats_ = self.gmm_lower_bound_ = self.gmm_n_iter_ = self.gmm_converged_ = None
         if self.hierarchical not in ('auto', 'device', 'host'):
             raise ValueError("hierarchical must be 'auto', 'device' or 'host'")
         self.partial_ = False
@@ -429,8 +457,12 @@ class ConsensusClustering:
         pam = None
         if Ks and km is None and hc is None:
             pam = _pam_route(_pam_spec(self.clusterer), X if cols is None else None)
+        gmm = None
+        if Ks and km is None and hc is None and pam is None:
+            gmm = _gmm_spec(self.clusterer)
         self.backend_ = ('gpu-kmeans' if km is not None else 'gpu-hc' if hc is not None
-                         else 'gpu-pam' if pam is not None else 'host-clusterer')
+                         else 'gpu-pam' if pam is not None else 'gpu-gmm' if gmm is not None
+                         else 'host-clusterer')
         precision = self.precision
         if precision == 'auto':
             # the reference's clusterer computes in X's dtype (CC.py:282): float64 input keeps
@@ -472,6 +504,11 @@ class ConsensusClustering:
             self.pam_inertia_ = torch.zeros((len(Ks), H), dtype=torch.float64, device=dev)
             self.pam_n_iter_ = torch.zeros((len(Ks), H), dtype=torch.int32, device=dev)
             self.pam_stats_ = self._fit_pam(X, wdtype, pam, idx_d, n, m, h0, h1, Ks, labels, dev, cols=cols)
+        elif Ks and gmm is not None:
+            self.gmm_lower_bound_ = torch.zeros((len(Ks), H), dtype=torch.float64, device=dev)
+            self.gmm_n_iter_ = torch.zeros((len(Ks), H), dtype=torch.int32, device=dev)
+            self.gmm_converged_ = torch.zeros((len(Ks), H), dtype=torch.uint8, device=dev)
+            self.gmm_stats_ = self._fit_gmm(X, wdtype, gmm, idx_d, n, m, h0, h1, Ks, labels, dev, cols=cols)
         elif Ks:
             if isinstance(X, torch.Tensor):
                 X = X.cpu().numpy()
@@ -579,6 +616,39 @@ class ConsensusClustering:
             lambda Dfull, Xd, cols_d, budget: engine.pam_labels(Dfull, idx_d, h0, h1, Ks, labels, budget=budget,
                                                                 max_iter=max_iter, X=Xd, cols_d=cols_d, metric=metric,
                                                                 inertia=self.pam_inertia_, n_iter=self.pam_n_iter_))
+
+    def _fit_gmm(self, X, wdtype, spec, idx_d, n, m, h0, h1, Ks, labels, dev, cols=None):
+        """CC.py:282 for GMM(**spec) on the device: the refusals from host values, the plan when a
+        workspace_budget is set (too small: raises before any launch), X as float64 on the device
+        (a float32 X is cast, with a warning: GMM computes in float64) and the column list, then
+        EM of every (resample, K) of [h0, h1) into this rank's columns of the label matrix, of
+        gmm_lower_bound_, gmm_n_iter_ and gmm_converged_ (engine.gmm_labels).  A problem with a
+        variance that is not positive raises sklearn's ValueError on every rank
+        (dist.first_failure)."""
+        if isinstance(X, torch.Tensor):
+            _gmm_validate(None if bool(torch.isfinite(X).all()) else X.detach().cpu().numpy(), m, Ks)
+        else:
+            _gmm_validate(X, m, Ks)
+        md = X.shape[1] if cols is None else cols.shape[1]
+        if self.workspace_budget is not None:
+            engine.gmm_plan(n, m, max(h1 - h0, 1), Ks, md, self.workspace_budget)
+        if np.dtype(wdtype) != np.float64:
+            warnings.warn("GMM computes in float64: the float32 X is cast to float64 (sklearn's GaussianMixture "
+                          "would compute in float32)", UserWarning)
+        X64 = (X.to(dev, torch.float64) if isinstance(X, torch.Tensor)
+               else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(dev)).contiguous()
+        cols_d = None if cols is None else torch.from_numpy(cols).to(dev)
+        stats = code = None
+        try:
+            stats = engine.gmm_labels(X64, idx_d, h0, h1, Ks, labels, budget=self.workspace_budget,
+                                      seed=int(self.random_state), cols_d=cols_d,
+                                      lower_bound=self.gmm_lower_bound_, n_iter=self.gmm_n_iter_,
+                                      converged=self.gmm_converged_, **spec)
+        except engine.IllDefinedMixture:
+            code = 1
+        if dist.first_failure(code, dev) is not None:
+            raise engine.IllDefinedMixture()
+        return stats
 
     def _fit_on_distances(self, X, wdtype, metric, n, m, Ks, dev, cols, validate, plan, run):
         """What the device clusterers over pdist(X, metric) share (the trees and PAM): the

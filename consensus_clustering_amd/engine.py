@@ -798,3 +798,166 @@ def pam_labels(Dfull: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, l
         stats['swap_iterations'] += pam_batch(D, rows, Ks_d, Kmax, a, labels, max_iter, inertia, n_iter, ws=ws)
         stats['launches'] += 1
     return stats
+
+
+# ---------------------------------------------------------------- GMM base clusterer
+
+class IllDefinedMixture(ValueError):
+    """A mixture problem met a variance that is not positive: sklearn's refusal, in its words."""
+
+    def __init__(self):
+        from .gmm import _ILL_DEFINED
+
+        super().__init__(_ILL_DEFINED)
+
+
+def _up256(v: int) -> int:
+    return (int(v) + 255) & ~255
+
+
+def gmm_bytes(m: int, md: int, Ks) -> int:
+    """Device bytes one resample of a GMM batch needs: its compact float64 rows [m, md], its row and
+    column indices and per K (Kp = K rounded up to 16) the responsibilities [m, Kp], the M-step
+    sums [Kp, 2 md + 1], the E-step's operand image [Kp, 2 md], three constants per component, the
+    16-row tile sums and the problem's 48-byte state: cc_gmm_workspace_bytes plus the rows."""
+    m, md = int(m), int(md)
+    per = 8 * m * md + 4 * m + 4 * md
+    for K in Ks:
+        Kp = (int(K) + 15) & ~15
+        per += _up256(8 * (m * Kp + Kp * (2 * md + 1) + Kp * 2 * md + 3 * Kp + (m + 15) // 16)) + 64
+    return per
+
+
+def gmm_plan(n: int, m: int, nh: int, Ks, md: int, budget: int) -> int:
+    """B = the resamples per batch for the nh resamples of a rank: as many as fit the budget next
+    to the init label matrix (uint8 [nK, n, B rounded up to 128]: nK * n bytes a resample and 127
+    columns of rounding), at most nh and at most 65535 problems a launch.  Raises when one
+    resample does not fit."""
+    nK = max(len(Ks), 1)
+    per = gmm_bytes(m, md, Ks) + nK * int(n)
+    fixed = 1024 + 127 * nK * int(n)
+    fit = (int(budget) - fixed) // per
+    if fit < 1:
+        raise ValueError(
+            f"workspace_budget = {int(budget)} bytes cannot hold the GMM clusterer: one resample "
+            f"of m = {int(m)} over {int(md)} features ({per + fixed} bytes) is needed")
+    return max(1, min(int(nh), int(fit), 65535 // nK))
+
+
+def gmm_workspace(m: int, md: int, B: int, Ks_h: np.ndarray, device) -> torch.Tensor:
+    nbytes = int(_lib.load().cc_gmm_workspace_bytes(int(m), int(md), int(B), Ks_h.ctypes.data, len(Ks_h)))
+    if nbytes == 0:
+        raise ValueError(f"GMM on the device needs 1 <= K <= min(m, 127), at most 127 values of K and at most "
+                         f"65535 problems a batch, got m = {m}, md = {md}, B = {B}, Ks = {Ks_h.tolist()}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def gmm_batch(X64: torch.Tensor, rows: torch.Tensor, cols_b, Ks, h_begin: int, labels: torch.Tensor,
+              n_init: int = 1, seed: int = 0, tol: float = 1e-3, reg_covar: float = 1e-6, max_iter: int = 100,
+              lower_bound: torch.Tensor = None, n_iter: torch.Tensor = None, converged: torch.Tensor = None,
+              ws: torch.Tensor = None, budget: int = None) -> int:
+    """GMM(n_components=K, n_init, random_state=seed, tol, reg_covar, max_iter) of every (resample b
+    of rows [B, m], K) over X64[rows[b]][:, cols_b[b]] (cols_b None: all columns): cc_gmm_gather,
+    then per init the k-means labels of the float64 engine (BatchedKMeans.run_f64 with
+    kpp_init = (init, n_init)), cc_gmm_start, cc_gmm_em_step until cc_gmm_active reads 0 or
+    max_iter iterations ran, and cc_gmm_finish into labels[k, rows[b, r], h_begin + b] (uint8
+    [nK, n, Hpad]) and lower_bound / n_iter / converged ([nK, H], at column h_begin + b) where the
+    init is the best so far.  budget: the workspace budget of the k-means fits.
+    Returns the EM iterations launched; raises IllDefinedMixture as sklearn does."""
+    from .kmeans import BatchedKMeans
+
+    assert X64.dtype == torch.float64 and X64.dim() == 2 and X64.is_contiguous() and X64.is_cuda
+    assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.is_contiguous()
+    n, d = X64.shape
+    B, m = rows.shape
+    dev = X64.device
+    md = d if cols_b is None else cols_b.shape[1]
+    Ks_h = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
+    nK = len(Ks_h)
+    assert labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous() and labels.shape[0] == nK
+    ldo = 0
+    for t, dt in ((lower_bound, torch.float64), (n_iter, torch.int32), (converged, torch.uint8)):
+        if t is not None:
+            assert t.dtype == dt and t.dim() == 2 and t.shape[0] == nK and t.is_contiguous()
+            assert ldo in (0, t.shape[1])
+            ldo = t.shape[1]
+    # an entry outside its range would be read out of bounds by the gather: checked here, on the
+    # device tensors, before anything is launched
+    lo, hi = (int(v) for v in torch.aminmax(rows))
+    if lo < 0 or hi >= n:
+        raise ValueError(f"idx entries must lie in [0, {n}), got [{lo}, {hi}]")
+    if cols_b is not None:
+        assert cols_b.dtype == torch.int32 and cols_b.dim() == 2 and cols_b.shape[0] == B and cols_b.is_contiguous()
+        lo, hi = (int(v) for v in torch.aminmax(cols_b))
+        if lo < 0 or hi >= d:
+            raise ValueError(f"cols entries must lie in [0, {d}), got [{lo}, {hi}]")
+    if ws is None:
+        ws = gmm_workspace(m, md, B, Ks_h, dev)
+    st = stream_ptr(dev)
+    Xb = torch.empty((B, m, md), dtype=torch.float64, device=dev)
+    with timed("cc_gmm_gather"):
+        _lib.call("cc_gmm_gather", X64.data_ptr(), n, d, rows.data_ptr(), _lib.ptr(cols_b), B, m, md, Xb.data_ptr(), st)
+    shape = (B, m, md, Ks_h.ctypes.data, nK)
+    lab = torch.empty((nK, n, pad_h(B)), dtype=torch.uint8, device=dev)  # each init's k-means labels
+    iterations = 0
+    active, failed = ctypes.c_int(0), ctypes.c_int(0)
+    for init in range(int(n_init)):
+        with timed("gmm_kmeans_init"):
+            bk = BatchedKMeans([int(K) for K in Ks_h], n_init=1, max_iter=300, tol=1e-4, random_state=seed,
+                               workspace_budget=budget)
+            bk.run_f64(X64, rows, n, B, m, 0, B, lab, cols_d=cols_b, kpp_init=(init, int(n_init)))
+        with timed("cc_gmm_start"):
+            _lib.call("cc_gmm_start", Xb.data_ptr(), rows.data_ptr(), B, m, md, Ks_h.ctypes.data, nK, lab.data_ptr(),
+                      n, lab.shape[2], 0, float(reg_covar), ws.data_ptr(), ws.numel(), st)
+        with timed("cc_gmm_em"):
+            for _ in range(int(max_iter)):
+                _lib.call("cc_gmm_em_step", Xb.data_ptr(), *shape, float(tol), float(reg_covar), int(max_iter),
+                          ws.data_ptr(), ws.numel(), st)
+                _lib.call("cc_gmm_active", ws.data_ptr(), ctypes.addressof(active), ctypes.addressof(failed), st)
+                iterations += 1
+                if active.value == 0:
+                    break
+        if failed.value:
+            raise IllDefinedMixture()
+        with timed("cc_gmm_finish"):
+            _lib.call("cc_gmm_finish", Xb.data_ptr(), rows.data_ptr(), *shape, int(init > 0), int(h_begin),
+                      labels.data_ptr(), labels.shape[1], labels.shape[2], _lib.ptr(lower_bound), _lib.ptr(n_iter),
+                      _lib.ptr(converged), ldo, ws.data_ptr(), ws.numel(), st)
+    return iterations
+
+
+def gmm_labels(X64: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, labels: torch.Tensor,
+               budget: int = None, n_init: int = 1, seed: int = 0, tol: float = 1e-3, reg_covar: float = 1e-6,
+               max_iter: int = 100, cols_d: torch.Tensor = None, lower_bound: torch.Tensor = None,
+               n_iter: torch.Tensor = None, converged: torch.Tensor = None) -> dict:
+    """Fill labels[k, idx[h, r], h] for h in [h0, h1) and every K of Ks with GMM(n_components=K, ...)
+    over X64[idx[h]] (float64 [n, d], device), under feature subsampling over X64[idx[h]][:, cols[h]]
+    (cols_d int32 [H, md], device, indexed by the global h like idx_d).  budget: device bytes for the
+    batches (default: half the free memory); lower_bound / n_iter / converged: optional [nK, H]
+    device tensors filled at the columns [h0, h1).  Returns dict(route='batched', batch, launches,
+    em_iterations, inits)."""
+    n, d = X64.shape
+    dev = X64.device
+    m = idx_d.shape[1]
+    md = d if cols_d is None else cols_d.shape[1]
+    nh = h1 - h0
+    Ks = [int(K) for K in Ks]
+    if budget is None:
+        budget = torch.cuda.mem_get_info(dev)[0] // 2
+    B = gmm_plan(n, m, max(nh, 1), Ks, md, budget)
+    stats = dict(route='batched', batch=B, launches=0, em_iterations=0, inits=int(n_init))
+    if cols_d is not None:
+        stats['feature_subsampling'] = md
+    if nh <= 0 or not Ks:
+        return stats
+    if min(Ks) < 1 or max(Ks) > m:
+        raise ValueError(f"every K must lie in [1, m = {m}], got {Ks}")
+    Ks_h = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
+    ws = gmm_workspace(m, md, B, Ks_h, dev)
+    for a in range(h0, h1, B):
+        b = min(a + B, h1)
+        stats['em_iterations'] += gmm_batch(
+            X64, idx_d[a:b].contiguous(), None if cols_d is None else cols_d[a:b].contiguous(), Ks, a, labels,
+            n_init, seed, tol, reg_covar, max_iter, lower_bound, n_iter, converged, ws=ws, budget=budget)
+        stats['launches'] += 1
+    return stats

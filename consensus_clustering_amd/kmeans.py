@@ -151,10 +151,13 @@ class BatchedKMeans:
         self.wide_calls = None
         self.calls = None  # the launch_plan of the last run
 
-    def _launch(self, dev, d, m, nh, precision, budget, budget_hard, weight_dtype, outputs, launch, grid=0):
+    def _launch(self, dev, d, m, nh, precision, budget, budget_hard, weight_dtype, outputs, launch, grid=0,
+                kpp_init=None):
         """Plan the fit for this device and the two byte budgets (CCMI_NSUB / CCMI_SEEDMAX override the
         units per resample / concurrent seeders) and make each call: launch(call, Ks, fit, ws) with
-        its K values, the arguments every engine takes from n_init to n_iter, the cached workspace."""
+        its K values, the arguments every engine takes from n_init to n_iter, the cached workspace.
+        kpp_init = (i, n): the k-means++ tables are built for n inits and init i's alone is handed
+        to the engine (run_f64)."""
         cus = torch.cuda.get_device_properties(dev).multi_processor_count
         self.calls = launch_plan(d, m, nh, self.Ks, self.n_init, precision, cus, budget, budget_hard,
                                  n_sub=int(os.environ.get("CCMI_NSUB", 0)),
@@ -164,7 +167,12 @@ class BatchedKMeans:
         for c in self.calls:
             k0 = c["k0"]
             Ks = np.ascontiguousarray(np.asarray(self.Ks[k0:k0 + c["nk"]], dtype=np.int32))
-            u, pos, stride = kpp_tables(Ks, self.n_init, self.seed, m, weight_dtype)
+            if kpp_init is None:
+                u, pos, stride = kpp_tables(Ks, self.n_init, self.seed, m, weight_dtype)
+            else:
+                u, pos, stride = kpp_tables(Ks, kpp_init[1], self.seed, m, weight_dtype)
+                u = np.ascontiguousarray(u[:, kpp_init[0]:kpp_init[0] + 1])
+                pos = np.ascontiguousarray(pos[:, kpp_init[0]:kpp_init[0] + 1])
             u_d = torch.from_numpy(u).to(dev)
             pos_d = torch.from_numpy(pos).to(dev)
             ws = workspace(dev, c["ws_bytes"])
@@ -219,8 +227,13 @@ class BatchedKMeans:
                             int(0.6 * torch.cuda.mem_get_info(dev)[0]), weight_dtype, outputs, wide)
 
     def run_f64(self, X64, idx_d, n, H, m, h_begin, h_end, labels_nh, inertia=None, n_iter=None,
-                grid=None, cols_d=None):
+                grid=None, cols_d=None, kpp_init=None):
         """float64 path (cc_kmeans_f64): X64 is the raw [n, d] float64 input on the device.
+
+        kpp_init = (i, n) (needs n_init = 1): run init i alone of the stream an n-init fit draws
+        from RandomState(seed).  Only k-means++ draws from it, so this is the i-th of n successive
+        KMeans(n_init=1, random_state=rs) fits on one RandomState rs (the initialisation of a
+        mixture model, engine.gmm_batch).  None: all n_init inits, the best kept.
 
         cols_d (feature subsampling, cc_kmeans_f64_cols): int32 [H, md] on X64's device, row h the
         ascending columns resample h is fitted on.  The fit is then planned at row width md.  A
@@ -229,6 +242,12 @@ class BatchedKMeans:
         dev = X64.device
         if max(self.Ks) > m:
             raise ValueError(f"n_samples={m} should be >= n_clusters={max(self.Ks)}.")
+        if kpp_init is not None:
+            i, of = (int(v) for v in kpp_init)
+            if self.n_init != 1 or not 0 <= i < of:
+                raise ValueError(f"kpp_init = (i, n) needs n_init = 1 and 0 <= i < n, got {kpp_init!r} with "
+                                 f"n_init = {self.n_init}")
+            kpp_init = (i, of)
         d = width = X64.shape[1]
         if cols_d is not None:
             if not (isinstance(cols_d, torch.Tensor) and cols_d.dtype == torch.int32 and cols_d.device == dev):
@@ -261,4 +280,4 @@ class BatchedKMeans:
         else:
             budget = hard = min(self.workspace_budget, free_half)
         return self._launch(dev, width, m, nh, 1, budget, hard, np.float64, (labels_nh, inertia, n_iter), f64,
-                            grid=grid)
+                            grid=grid, kpp_init=kpp_init)

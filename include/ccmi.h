@@ -39,6 +39,10 @@
  *   cc_pam_build, cc_pam_swap_step, cc_pam_active, cc_pam_labels
  *                         CC.py:282 for the PAM (k-medoids) base clusterer: BUILD and SWAP of
  *                         every (resample, K) problem over the same [B][m][m] distances
+ *   cc_gmm_gather, cc_gmm_start, cc_gmm_em_step, cc_gmm_active, cc_gmm_finish
+ *                         CC.py:282 for the GMM base clusterer (diagonal Gaussian mixture, sklearn's
+ *                         GaussianMixture(covariance_type='diag') in float64): batched EM of every
+ *                         (resample, K) problem from a k-means initialisation, best of n_init
  */
 #ifndef CCMI_H
 #define CCMI_H
@@ -351,6 +355,63 @@ int cc_pam_active(const void* workspace, int* active, void* stream);
 int cc_pam_labels(const double* D, const int* idx, int B, int m, const int* Ks, int nK, int Kmax, int h_begin,
                   uint8_t* labels, int64_t n, int64_t ldl, double* inertia, int* n_iter, int64_t ldo, int* medoids,
                   void* workspace, size_t ws_bytes, void* stream);
+
+/* GMM: EM for the mixture of Ks[k] Gaussians with diagonal covariances (sklearn 1.7's
+ * GaussianMixture(covariance_type='diag') in float64, restated in gmm.py) on each of B resamples'
+ * rows Xb [B][m][md] (float64, finite, the batch cc_gmm_gather makes).  Problem (b, k) has Ks[k]
+ * components.  Ks [nK] int32 on the HOST (it sizes the workspace), 1 <= Ks[k] <= min(m, 127),
+ * nK <= 127, B * nK <= 65535, md >= 1.  All arithmetic is float64, both contractions run on the
+ * float64 matrix cores and no sum uses a floating-point atomic or depends on the grid or the
+ * batch: the same inputs give bitwise the same lower bound on every run and under every batching.
+ * Another conforming implementation adds in another order, so its lower bound differs by about
+ * m * 2^-52 relative and a decision (converged, the winning init, a row's component) may fall
+ * differently where its margin is that small.
+ *
+ * cc_gmm_workspace_bytes: the workspace of the calls below (0 for arguments they refuse); it holds
+ * per problem the responsibilities (8 m Kp bytes, Kp = Ks[k] rounded up to 16), the M-step sums,
+ * the E-step's operand image and the 16-row tile sums.  One workspace carries a batch through
+ * every init: cc_gmm_start, cc_gmm_em_step until cc_gmm_active reads 0, cc_gmm_finish. */
+size_t cc_gmm_workspace_bytes(int m, int md, int B, const int* Ks, int nK);
+
+/* Xb[b][r][c] = X[idx[b][r]][cols ? cols[b][c] : c]: the rows of B resamples under their own
+ * columns.  X [n][d] float64; idx [B][m] int32 and cols (NULL = all columns, md = d; else [B][md]
+ * int32) on the device, read as given: the caller checks their ranges. */
+int cc_gmm_gather(const double* X, int64_t n, int d, const int* idx, const int* cols, int B, int m, int md,
+                  double* Xb, void* stream);
+
+/* Start one init of every problem: the one-hot responsibilities from the init labels
+ * init_labels uint8 [nK][n][ldl], read at [k][idx[b][r]][col_begin + b] (a label outside
+ * [0, Ks[k]) gives the row to no component), then sklearn's _initialize (the M-step with
+ * weights = counts / m) and the problem's state: n_iter 0, previous bound -inf, active.  The best
+ * bound of earlier inits is kept.  Asynchronous on `stream`. */
+int cc_gmm_start(const double* Xb, const int* idx, int B, int m, int md, const int* Ks, int nK,
+                 const uint8_t* init_labels, int64_t n, int64_t ldl, int col_begin, double reg_covar,
+                 void* workspace, size_t ws_bytes, void* stream);
+
+/* One EM iteration of every problem that is still active: the E-step (log probabilities as one
+ * GEMM of [x, x^2] against [-2 mean prec ; prec], scipy's logsumexp per row, the lower bound = the
+ * mean of the row log-norms), the M-step (resp^T [x, x^2, 1]; weights divided by their sum;
+ * variances avg_x2 - mean^2 + reg_covar), and the decision: converged when
+ * |bound - previous| < tol, stopped unconverged at max_iter iterations.  A finished problem is
+ * left alone by later calls.  A variance that is not positive marks the problem failed.  The
+ * number of problems still active is left in the workspace for cc_gmm_active. */
+int cc_gmm_em_step(const double* Xb, int B, int m, int md, const int* Ks, int nK, double tol, double reg_covar,
+                   int max_iter, void* workspace, size_t ws_bytes, void* stream);
+
+/* Synchronises `stream` and stores in *active (host) how many problems the last cc_gmm_em_step
+ * left active (0 = every problem is finished) and in *failed (host, may be NULL) how many
+ * problems of the batch have failed since cc_gmm_start. */
+int cc_gmm_active(const void* workspace, int* active, int* failed, void* stream);
+
+/* The results of one init: with keep_best = 0 (the first init) of every problem, else of the
+ * problems whose lower bound is strictly larger than the best of the inits before.  For those,
+ * a final E-step under the init's parameters gives labels[k][idx[b][r]][h_begin + b] = the
+ * component of the largest log responsibility (first index on ties); labels uint8 [nK][n][ldl].
+ * lower_bound [nK][ldo] float64, n_iter [nK][ldo] int32 and converged [nK][ldo] uint8 (each may be
+ * NULL) receive the init's values at [k][h_begin + b]. */
+int cc_gmm_finish(const double* Xb, const int* idx, int B, int m, int md, const int* Ks, int nK, int keep_best,
+                  int h_begin, uint8_t* labels, int64_t n, int64_t ldl, double* lower_bound, int* n_iter,
+                  uint8_t* converged, int64_t ldo, void* workspace, size_t ws_bytes, void* stream);
 
 /* Batched k-means for every (resample h, K, init) problem, replacing the per-(K, h)
  * clusterer.fit_predict(X[indices]) of CC.py:282 for the default clusterer
