@@ -22,9 +22,11 @@ What runs where (``fit``):
                   (K, h) and only its labels go to the GPU (hybrid path); PAM (pam.py, k-medoids
                   under the same four metrics) -> BUILD and SWAP of every (resample, K) on the
                   device over the same distances (cc_pam_build, cc_pam_swap_step, cc_pam_labels);
-                  GMM (gmm.py, sklearn's diagonal Gaussian mixture in float64) -> batched EM of
+                  GMM, FullGMM (gmm.py, sklearn's diagonal and full-covariance Gaussian mixtures in
+                  float64; gmm_covariance_type_ tells which) -> batched EM of
                   every (resample, K), each init started from the float64 k-means engine's labels
-                  (cc_gmm_gather, cc_gmm_start, cc_gmm_em_step, cc_gmm_finish)
+                  (cc_gmm_gather, cc_gmm_start, cc_gmm_em_step, cc_gmm_finish; FullGMM:
+                  cc_gmm_full_start, cc_gmm_full_em_step, cc_gmm_full_finish, at most 128 features)
   I, M, histogram int8-MFMA tiles of the upper triangle (cc_cosample / cc_coassoc)
   hist/cdf/PAC    host float64 from 20 exact integer counts (post.py)
   multi-GPU       resamples and triangle tiles sharded over torch.distributed ranks
@@ -56,7 +58,7 @@ from .kmeans import BatchedKMeans
 from .pam import METRICS as HC_METRICS  # sklearn's metric spellings -> scipy's names
 from .pam import PAM, degenerate_rows as _hc_degenerate, refuse_not_finite
 from .pam import validate as _pam_validate
-from .gmm import GMM, validate as _gmm_validate
+from .gmm import GMM, FullGMM, validate as _gmm_validate
 
 KMAX = 127  # largest K: uint8 labels (0xFF = not sampled) and int8 one-hot channels
 
@@ -231,6 +233,20 @@ def _gmm_spec(est):
     p = est.get_params()
     if not isinstance(p.get("covariance_type"), str) or p["covariance_type"] != 'diag':
         return None
+    return _gmm_params(p)
+
+
+def _gmm_full_spec(est):
+    """_gmm_spec for the full-covariance model (cc_gmm_full_start, cc_gmm_full_em_step,
+    cc_gmm_full_finish): exactly the type FullGMM, under the same rules for its parameters."""
+    if type(est) is not FullGMM:
+        return None
+    return _gmm_params(est.get_params())
+
+
+def _gmm_params(p):
+    """The parameter dict p as the device takes it, else None: integer max_iter >= 1 and
+    n_init >= 1, finite tol >= 0 and reg_covar >= 0."""
     for name in ("max_iter", "n_init"):
         v = p.get(name)
         if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
@@ -385,6 +401,7 @@ class ConsensusClustering:
         self.hc_stats_ = self.hc_metric_ = None
         self.pam_stats_ = self.pam_metric_ = self.pam_inertia_ = self.pam_n_iter_ = None
         self.gmm_stats_ = self.gmm_lower_bound_ = self.gmm_n_iter_ = self.gmm_converged_ = None
+        self.gmm_covariance_type_ = None
         if self.hierarchical not in ('auto', 'device', 'host'):
             raise ValueError("hierarchical must be 'auto', 'device' or 'host'")
         self.partial_ = False
@@ -460,6 +477,14 @@ class ConsensusClustering:
         gmm = None
         if Ks and km is None and hc is None and pam is None:
             gmm = _gmm_spec(self.clusterer)
+            self.gmm_covariance_type_ = 'diag' if gmm is not None else None
+            if gmm is None:
+                gmm = _gmm_full_spec(self.clusterer)
+                if gmm is not None and md > engine.GMM_FULL_MD_MAX:
+                    warnings.warn(f"FullGMM runs on the device for at most {engine.GMM_FULL_MD_MAX} features: with "
+                                  f"{md} features the fits run on the host (one fit per resample and K)", UserWarning)
+                    gmm = None
+                self.gmm_covariance_type_ = 'full' if gmm is not None else None
         self.backend_ = ('gpu-kmeans' if km is not None else 'gpu-hc' if hc is not None
                          else 'gpu-pam' if pam is not None else 'gpu-gmm' if gmm is not None
                          else 'host-clusterer')
@@ -618,20 +643,23 @@ class ConsensusClustering:
                                                                 inertia=self.pam_inertia_, n_iter=self.pam_n_iter_))
 
     def _fit_gmm(self, X, wdtype, spec, idx_d, n, m, h0, h1, Ks, labels, dev, cols=None):
-        """CC.py:282 for GMM(**spec) on the device: the refusals from host values, the plan when a
+        """CC.py:282 for GMM(**spec), or FullGMM(**spec) where gmm_covariance_type_ is 'full', on the
+        device: the refusals from host values, the plan when a
         workspace_budget is set (too small: raises before any launch), X as float64 on the device
         (a float32 X is cast, with a warning: GMM computes in float64) and the column list, then
         EM of every (resample, K) of [h0, h1) into this rank's columns of the label matrix, of
         gmm_lower_bound_, gmm_n_iter_ and gmm_converged_ (engine.gmm_labels).  A problem with a
-        variance that is not positive raises sklearn's ValueError on every rank
+        variance (a Cholesky pivot under 'full') that is not positive raises sklearn's ValueError on every rank
         (dist.first_failure)."""
+        covariance = self.gmm_covariance_type_
+        who = "FullGMM" if covariance == 'full' else "GMM"
         if isinstance(X, torch.Tensor):
-            _gmm_validate(None if bool(torch.isfinite(X).all()) else X.detach().cpu().numpy(), m, Ks)
+            _gmm_validate(None if bool(torch.isfinite(X).all()) else X.detach().cpu().numpy(), m, Ks, who)
         else:
-            _gmm_validate(X, m, Ks)
+            _gmm_validate(X, m, Ks, who)
         md = X.shape[1] if cols is None else cols.shape[1]
         if self.workspace_budget is not None:
-            engine.gmm_plan(n, m, max(h1 - h0, 1), Ks, md, self.workspace_budget)
+            engine.gmm_plan(n, m, max(h1 - h0, 1), Ks, md, self.workspace_budget, covariance)
         if np.dtype(wdtype) != np.float64:
             warnings.warn("GMM computes in float64: the float32 X is cast to float64 (sklearn's GaussianMixture "
                           "would compute in float32)", UserWarning)
@@ -643,7 +671,7 @@ class ConsensusClustering:
             stats = engine.gmm_labels(X64, idx_d, h0, h1, Ks, labels, budget=self.workspace_budget,
                                       seed=int(self.random_state), cols_d=cols_d,
                                       lower_bound=self.gmm_lower_bound_, n_iter=self.gmm_n_iter_,
-                                      converged=self.gmm_converged_, **spec)
+                                      converged=self.gmm_converged_, covariance=covariance, **spec)
         except engine.IllDefinedMixture:
             code = 1
         if dist.first_failure(code, dev) is not None:

@@ -19,50 +19,14 @@
 // floating-point atomic anywhere):
 //   GEMM chains   v_mfma_f64_16x16x4_f64 accumulates the sequential FMA chain over its inner index
 //                 (see kmeans_f64.hip): j = 0 .. 2 md - 1 in the E-step, r = 0 .. m - 1 in the M-step
-//   logsumexp     per row, lane q = 0..3 adds its components q, q + 4, .. in order, then (q0 + q1) +
-//                 (q2 + q3)
-//   lower bound   per 16-row tile rows 0..15 in order; per problem lane l adds tiles l, l + 64, .. in
-//                 order, then a butterfly over the 64 lanes
+//   logsumexp, lower bound   gmm_shared.hpp: the row tail of the E-step, gmm_decide and gmm_pick,
+//                 which the full-covariance kernels (gmm_full.hip) share with this file
 //   per component constants   j = 0 .. md - 1 in order; the weight sum c = 0 .. K - 1 in order
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-#include <string>
-
-#include "ccmi_internal.h"
-
-#pragma clang fp contract(off)
+#include "gmm_shared.hpp"
 
 namespace {
 
-constexpr int GT = 256;  // threads of a workgroup
-constexpr int GW = GT / 64;
-constexpr int GMM_KMAX = 127;
-constexpr int GMM_NKMAX = 127;
 constexpr int ESTEP_CHUNKS = 128;  // most workgroups along the rows of one problem
-constexpr size_t HEADER = 256;     // word[0]: problems still active, word[1]: problems that failed
-
-using f64x4 = __attribute__((ext_vector_type(4))) double;
-
-struct State {
-  double prev, lower, best;  // the bound before and after the last E-step; the best init's so far
-  int n_iter, active, converged, failed, win, mrun;
-};
-
-struct Args {
-  int m, md, B, nK;
-  int Ks[GMM_NKMAX];
-  unsigned long long off[GMM_NKMAX];  // bytes from a resample's block to the arrays of K index k
-  unsigned long long per_b;           // bytes of one resample's block
-  int* word;
-  State* st;
-  char* base;
-  const double* Xb;
-};
-
-__host__ __device__ inline int pad16(int K) { return (K + 15) & ~15; }
-__host__ __device__ inline size_t up256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
 
 // the arrays of one problem, in this order: resp [m][Kp], sums [Kp][2 md + 1], W [Kp][2 md],
 // cst / ldet / logw [Kp] each, part [ceil(m / 16)]
@@ -102,27 +66,6 @@ __global__ __launch_bounds__(GT) void gmm_gather(const double* __restrict__ X, i
   const int r = static_cast<int>(e / md), c = static_cast<int>(e % md);
   const int col = cols ? cols[static_cast<size_t>(b) * md + c] : c;
   Xb[static_cast<size_t>(b) * m * md + e] = X[static_cast<size_t>(idx[static_cast<size_t>(b) * m + r]) * d + col];
-}
-
-// the one-hot responsibilities of every problem from the init labels, and the state reset
-__global__ __launch_bounds__(GT) void gmm_onehot(Args a, const int* __restrict__ idx, const uint8_t* __restrict__ lab,
-                                                 int64_t n, int64_t ldl, int col_begin) {
-  const int p = blockIdx.y, b = p / a.nK, k = p % a.nK;
-  const Prob pr = prob(a, b, k);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    State& s = a.st[p];
-    s.prev = s.lower = -INFINITY;
-    s.n_iter = 0;
-    s.active = 1;
-    s.converged = s.failed = s.win = s.mrun = 0;
-  }
-  const uint8_t* L = lab + static_cast<size_t>(k) * n * ldl + col_begin + b;
-  for (int r = blockIdx.x * GT + threadIdx.x; r < a.m; r += gridDim.x * GT) {
-    const int item = idx[static_cast<size_t>(b) * a.m + r];
-    const int l = item >= 0 && item < n ? L[static_cast<int64_t>(item) * ldl] : 0xFF;
-    double* row = pr.resp + static_cast<size_t>(r) * pr.Kp;
-    for (int c = 0; c < pr.Kp; ++c) row[c] = c == l ? 1.0 : 0.0;
-  }
 }
 
 // mode 0: one E-step of the active problems (resp, tile sums); mode 1: the labels of the problems
@@ -172,104 +115,9 @@ __global__ __launch_bounds__(GT) void gmm_estep(Args a, const int* __restrict__ 
       }
     }
     __syncthreads();
-    // row lr, components q, q + 4, ..
-    double mx = -INFINITY;
-    for (int c = q; c < Kp; c += 4) mx = fmax(mx, wl[c * 16 + lr]);
-    mx = fmax(mx, __shfl_xor(mx, 16));
-    mx = fmax(mx, __shfl_xor(mx, 32));
-    double sum = 0.0;
-    int cnt = 0;
-    for (int c = q; c < Kp; c += 4) {
-      const double v = wl[c * 16 + lr];
-      if (v == mx)
-        ++cnt;
-      else
-        sum += exp(v - mx);
-    }
-    cnt += __shfl_xor(cnt, 16);
-    cnt += __shfl_xor(cnt, 32);
-    sum += __shfl_xor(sum, 16);
-    sum += __shfl_xor(sum, 32);
-    if (sum != 0.0) sum = sum / cnt;
-    const double ln = (log1p(sum) + log(static_cast<double>(cnt))) + mx;
-    if (MODE == 0) {
-      // component ct * 16 + lr, rows q, q + 4, ..: 128-byte pieces of resp
-      for (int i = 0; i < 4; ++i) {
-        const int rl = q + 4 * i;
-        const double lnr = __shfl(ln, rl);
-        const int grow = tile * 16 + rl;
-        for (int ct = 0; ct < nct; ++ct) {
-          const int c = ct * 16 + lr;
-          const double r = exp(wl[c * 16 + rl] - lnr);
-          if (valid && grow < m) pr.resp[static_cast<size_t>(grow) * Kp + c] = c < K ? r : 0.0;
-        }
-      }
-      double t = 0.0;
-      for (int r = 0; r < 16; ++r) {
-        const double v = __shfl(ln, r);
-        if (tile * 16 + r < m) t += v;
-      }
-      if (valid && lane == 0) pr.part[tile] = t;
-    } else {
-      double best = -INFINITY;
-      int bi = 0x7fffffff;
-      for (int c = q; c < K; c += 4) {
-        const double v = wl[c * 16 + lr] - ln;
-        if (v > best) {
-          best = v;
-          bi = c;
-        }
-      }
-#pragma unroll
-      for (int o = 16; o <= 32; o <<= 1) {
-        const double b2 = __shfl_xor(best, o);
-        const int i2 = __shfl_xor(bi, o);
-        if (b2 > best || (b2 == best && i2 < bi)) {
-          best = b2;
-          bi = i2;
-        }
-      }
-      if (bi == 0x7fffffff) bi = 0;
-      if (rin && q == 0) {
-        const int item = idx[static_cast<size_t>(b) * m + row];
-        if (item >= 0 && item < n)
-          labels[static_cast<size_t>(k) * n * ldl + static_cast<int64_t>(item) * ldl + h_begin + b] =
-              static_cast<uint8_t>(bi);
-      }
-    }
+    gmm_row_tail<MODE>(wl, K, Kp, m, tile, valid, pr.resp, pr.part, idx + static_cast<size_t>(b) * m, labels,
+                       static_cast<size_t>(k) * n * ldl + h_begin + b, n, ldl);
     __syncthreads();
-  }
-}
-
-// one wave per problem: the bound of the E-step just run, and what it decides
-__global__ __launch_bounds__(GT) void gmm_decide(Args a, double tol, int max_iter) {
-  const int p = blockIdx.x * GW + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (p >= a.B * a.nK) return;
-  State& s = a.st[p];
-  if (!s.active) {
-    if (lane == 0) s.mrun = 0;
-    return;
-  }
-  const Prob pr = prob(a, p / a.nK, p % a.nK);
-  const int ntile = (a.m + 15) >> 4;
-  double t = 0.0;
-  for (int i = lane; i < ntile; i += 64) t += pr.part[i];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o);
-  if (lane == 0) {
-    const double lower = t / a.m;
-    const double change = lower - s.prev;
-    s.lower = s.prev = lower;
-    s.n_iter += 1;
-    s.mrun = 1;
-    if (fabs(change) < tol) {
-      s.converged = 1;
-      s.active = 0;
-    } else if (s.n_iter >= max_iter) {
-      s.active = 0;
-    } else {
-      atomicAdd(a.word, 1);
-    }
   }
 }
 
@@ -360,76 +208,15 @@ __global__ __launch_bounds__(GT) void gmm_mstep(Args a, int init, double reg_cov
     pr.logw[tid] = lw;
   }
   __syncthreads();
-  if (tid == 0 && bad_s) {  // sklearn's "ill-defined empirical covariance": the batch is refused
-    State& s = a.st[p];
-    if (!s.failed) atomicAdd(a.word + 1, 1);
-    s.failed = 1;
-    s.active = 0;
-  }
-}
-
-// which problems this init wins, and their scalar outputs
-__global__ __launch_bounds__(GT) void gmm_pick(Args a, int keep_best, int h_begin, double* lower_bound, int* n_iter,
-                                               uint8_t* converged, int64_t ldo) {
-  const int p = blockIdx.x * GT + threadIdx.x;
-  if (p >= a.B * a.nK) return;
-  State& s = a.st[p];
-  const bool win = !keep_best || s.lower > s.best || s.best == -INFINITY;
-  s.win = win;
-  if (!win) return;
-  s.best = s.lower;
-  const int64_t at = static_cast<int64_t>(p % a.nK) * ldo + h_begin + p / a.nK;
-  if (lower_bound) lower_bound[at] = s.lower;
-  if (n_iter) n_iter[at] = s.n_iter;
-  if (converged) converged[at] = static_cast<uint8_t>(s.converged);
-}
-
-int launch_error(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    cc::set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return CC_ERR_HIP;
-  }
-  return CC_OK;
+  if (tid == 0 && bad_s) gmm_mark_failed(a.word, a.st[p]);
 }
 
 bool shape_ok(int m, int md, int B, const int* Ks, int nK) {
-  if (!Ks || m < 1 || m > (1 << 24) || md < 1 || md > (1 << 20) || B < 1 || B > 65535 || nK < 1 || nK > GMM_NKMAX)
-    return false;
-  for (int k = 0; k < nK; ++k)
-    if (Ks[k] < 1 || Ks[k] > GMM_KMAX || Ks[k] > m) return false;
-  return static_cast<size_t>(B) * nK <= 65535;  // the problems are a grid's y extent
+  return md >= 1 && md <= (1 << 20) && batch_ok(m, B, Ks, nK);
 }
 
-// the workspace: header, the states, then per resample the arrays of every K
 size_t layout(int m, int md, int B, const int* Ks, int nK, void* ws, Args* a) {
-  const size_t states = up256(static_cast<size_t>(B) * nK * sizeof(State));
-  size_t per_b = 0;
-  for (int k = 0; k < nK; ++k) {
-    if (a) {
-      a->Ks[k] = Ks[k];
-      a->off[k] = per_b;
-    }
-    per_b += up256(8 * prob_doubles(m, md, Ks[k]));
-  }
-  if (a) {
-    a->m = m;
-    a->md = md;
-    a->B = B;
-    a->nK = nK;
-    a->per_b = per_b;
-    a->word = static_cast<int*>(ws);
-    a->st = reinterpret_cast<State*>(static_cast<char*>(ws) + HEADER);
-    a->base = static_cast<char*>(ws) + HEADER + states;
-    a->Xb = nullptr;
-  }
-  return HEADER + states + static_cast<size_t>(B) * per_b;
-}
-
-int max_kp(const int* Ks, int nK) {
-  int v = 0;
-  for (int k = 0; k < nK; ++k) v = pad16(Ks[k]) > v ? pad16(Ks[k]) : v;
-  return v;
+  return layout(prob_doubles, m, md, B, Ks, nK, ws, a);
 }
 
 dim3 estep_grid(int m, int B, int nK) {
@@ -472,7 +259,7 @@ extern "C" int cc_gmm_start(const double* Xb, const int* idx, int B, int m, int 
   const hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(workspace, 0, HEADER, st) != hipSuccess) return launch_error("cc_gmm_start");
   const int chunks = (m + GT - 1) / GT;
-  hipLaunchKernelGGL(gmm_onehot, dim3(chunks < 64 ? chunks : 64, B * nK), dim3(GT), 0, st, a, idx, init_labels, n, ldl,
+  hipLaunchKernelGGL(gmm_onehot<Args>, dim3(chunks < 64 ? chunks : 64, B * nK), dim3(GT), 0, st, a, idx, init_labels, n, ldl,
                      col_begin);
   hipLaunchKernelGGL(gmm_mstep, dim3(B * nK), dim3(GT), 0, st, a, 1, reg_covar);
   return launch_error("cc_gmm_start");
@@ -493,7 +280,7 @@ extern "C" int cc_gmm_em_step(const double* Xb, int B, int m, int md, const int*
   const size_t lds = static_cast<size_t>(GW) * max_kp(Ks, nK) * 16 * sizeof(double);
   hipLaunchKernelGGL(gmm_estep<0>, estep_grid(m, B, nK), dim3(GT), lds, st, a, static_cast<const int*>(nullptr),
                      static_cast<uint8_t*>(nullptr), static_cast<int64_t>(0), static_cast<int64_t>(0), 0);
-  hipLaunchKernelGGL(gmm_decide, dim3((B * nK + GW - 1) / GW), dim3(GT), 0, st, a, tol, max_iter);
+  hipLaunchKernelGGL(gmm_decide<Args>, dim3((B * nK + GW - 1) / GW), dim3(GT), 0, st, a, tol, max_iter);
   hipLaunchKernelGGL(gmm_mstep, dim3(B * nK), dim3(GT), 0, st, a, 0, reg_covar);
   return launch_error("cc_gmm_em_step");
 }
@@ -530,7 +317,7 @@ extern "C" int cc_gmm_finish(const double* Xb, const int* idx, int B, int m, int
   layout(m, md, B, Ks, nK, workspace, &a);
   a.Xb = Xb;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(gmm_pick, dim3((B * nK + GT - 1) / GT), dim3(GT), 0, st, a, keep_best, h_begin, lower_bound,
+  hipLaunchKernelGGL(gmm_pick<Args>, dim3((B * nK + GT - 1) / GT), dim3(GT), 0, st, a, keep_best, h_begin, lower_bound,
                      n_iter, converged, ldo);
   const size_t lds = static_cast<size_t>(GW) * max_kp(Ks, nK) * 16 * sizeof(double);
   hipLaunchKernelGGL(gmm_estep<1>, estep_grid(m, B, nK), dim3(GT), lds, st, a, idx, labels, n, ldl, h_begin);

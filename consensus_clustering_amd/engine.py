@@ -803,7 +803,8 @@ def pam_labels(Dfull: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, l
 # ---------------------------------------------------------------- GMM base clusterer
 
 class IllDefinedMixture(ValueError):
-    """A mixture problem met a variance that is not positive: sklearn's refusal, in its words."""
+    """A mixture problem met a variance that is not positive, or a covariance whose Cholesky
+    factorisation met a pivot that is not: sklearn's refusal, in its words."""
 
     def __init__(self):
         from .gmm import _ILL_DEFINED
@@ -828,13 +829,31 @@ def gmm_bytes(m: int, md: int, Ks) -> int:
     return per
 
 
-def gmm_plan(n: int, m: int, nh: int, Ks, md: int, budget: int) -> int:
+GMM_FULL_MD_MAX = 128  # the most features of the full-covariance kernels (csrc/gmm_full.hip)
+
+
+def gmm_full_bytes(m: int, md: int, Ks) -> int:
+    """gmm_bytes for the full-covariance model: next to the rows, the indices and per K the
+    responsibilities [m, Kp], the M-step sums [Kp, md + 1], the means [Kp, md], the factors
+    [K, md, md] (each covariance's lower triangle, then its precision factor in place), mu P
+    [Kp, md], three constants per component, the 16-row tile sums and the state:
+    cc_gmm_full_workspace_bytes plus the rows."""
+    m, md = int(m), int(md)
+    per = 8 * m * md + 4 * m + 4 * md
+    for K in Ks:
+        K = int(K)
+        Kp = (K + 15) & ~15
+        per += _up256(8 * (m * Kp + Kp * (md + 1) + Kp * md + K * md * md + Kp * md + 3 * Kp + (m + 15) // 16)) + 64
+    return per
+
+
+def gmm_plan(n: int, m: int, nh: int, Ks, md: int, budget: int, covariance: str = 'diag') -> int:
     """B = the resamples per batch for the nh resamples of a rank: as many as fit the budget next
     to the init label matrix (uint8 [nK, n, B rounded up to 128]: nK * n bytes a resample and 127
     columns of rounding), at most nh and at most 65535 problems a launch.  Raises when one
     resample does not fit."""
     nK = max(len(Ks), 1)
-    per = gmm_bytes(m, md, Ks) + nK * int(n)
+    per = (gmm_full_bytes if covariance == 'full' else gmm_bytes)(m, md, Ks) + nK * int(n)
     fixed = 1024 + 127 * nK * int(n)
     fit = (int(budget) - fixed) // per
     if fit < 1:
@@ -844,10 +863,24 @@ def gmm_plan(n: int, m: int, nh: int, Ks, md: int, budget: int) -> int:
     return max(1, min(int(nh), int(fit), 65535 // nK))
 
 
-def gmm_workspace(m: int, md: int, B: int, Ks_h: np.ndarray, device) -> torch.Tensor:
-    nbytes = int(_lib.load().cc_gmm_workspace_bytes(int(m), int(md), int(B), Ks_h.ctypes.data, len(Ks_h)))
+def gmm_full_plan(n: int, m: int, nh: int, Ks, md: int, budget: int) -> int:
+    """gmm_plan for the full-covariance model."""
+    return gmm_plan(n, m, nh, Ks, md, budget, 'full')
+
+
+def _gmm_entry(covariance: str, name: str) -> str:
+    """The entry point `name` (workspace_bytes, start, em_step, finish) of the covariance type."""
+    if covariance not in ('diag', 'full'):
+        raise ValueError(f"covariance must be 'diag' or 'full', got {covariance!r}")
+    return ("cc_gmm_full_" if covariance == 'full' else "cc_gmm_") + name
+
+
+def gmm_workspace(m: int, md: int, B: int, Ks_h: np.ndarray, device, covariance: str = 'diag') -> torch.Tensor:
+    fn = getattr(_lib.load(), _gmm_entry(covariance, "workspace_bytes"))
+    nbytes = int(fn(int(m), int(md), int(B), Ks_h.ctypes.data, len(Ks_h)))
     if nbytes == 0:
-        raise ValueError(f"GMM on the device needs 1 <= K <= min(m, 127), at most 127 values of K and at most "
+        limit = f", at most {GMM_FULL_MD_MAX} features" if covariance == 'full' else ""
+        raise ValueError(f"GMM on the device needs 1 <= K <= min(m, 127), at most 127 values of K{limit} and at most "
                          f"65535 problems a batch, got m = {m}, md = {md}, B = {B}, Ks = {Ks_h.tolist()}")
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
@@ -855,8 +888,9 @@ def gmm_workspace(m: int, md: int, B: int, Ks_h: np.ndarray, device) -> torch.Te
 def gmm_batch(X64: torch.Tensor, rows: torch.Tensor, cols_b, Ks, h_begin: int, labels: torch.Tensor,
               n_init: int = 1, seed: int = 0, tol: float = 1e-3, reg_covar: float = 1e-6, max_iter: int = 100,
               lower_bound: torch.Tensor = None, n_iter: torch.Tensor = None, converged: torch.Tensor = None,
-              ws: torch.Tensor = None, budget: int = None) -> int:
-    """GMM(n_components=K, n_init, random_state=seed, tol, reg_covar, max_iter) of every (resample b
+              ws: torch.Tensor = None, budget: int = None, covariance: str = 'diag') -> int:
+    """GMM (covariance 'diag') or FullGMM ('full': the cc_gmm_full_ entry points below, md <= 128)
+    (n_components=K, n_init, random_state=seed, tol, reg_covar, max_iter) of every (resample b
     of rows [B, m], K) over X64[rows[b]][:, cols_b[b]] (cols_b None: all columns): cc_gmm_gather,
     then per init the k-means labels of the float64 engine (BatchedKMeans.run_f64 with
     kpp_init = (init, n_init)), cc_gmm_start, cc_gmm_em_step until cc_gmm_active reads 0 or
@@ -892,7 +926,8 @@ def gmm_batch(X64: torch.Tensor, rows: torch.Tensor, cols_b, Ks, h_begin: int, l
         if lo < 0 or hi >= d:
             raise ValueError(f"cols entries must lie in [0, {d}), got [{lo}, {hi}]")
     if ws is None:
-        ws = gmm_workspace(m, md, B, Ks_h, dev)
+        ws = gmm_workspace(m, md, B, Ks_h, dev, covariance)
+    start, em_step, finish = (_gmm_entry(covariance, name) for name in ("start", "em_step", "finish"))
     st = stream_ptr(dev)
     Xb = torch.empty((B, m, md), dtype=torch.float64, device=dev)
     with timed("cc_gmm_gather"):
@@ -907,11 +942,11 @@ def gmm_batch(X64: torch.Tensor, rows: torch.Tensor, cols_b, Ks, h_begin: int, l
                                workspace_budget=budget)
             bk.run_f64(X64, rows, n, B, m, 0, B, lab, cols_d=cols_b, kpp_init=(init, int(n_init)))
         with timed("cc_gmm_start"):
-            _lib.call("cc_gmm_start", Xb.data_ptr(), rows.data_ptr(), B, m, md, Ks_h.ctypes.data, nK, lab.data_ptr(),
+            _lib.call(start, Xb.data_ptr(), rows.data_ptr(), B, m, md, Ks_h.ctypes.data, nK, lab.data_ptr(),
                       n, lab.shape[2], 0, float(reg_covar), ws.data_ptr(), ws.numel(), st)
         with timed("cc_gmm_em"):
             for _ in range(int(max_iter)):
-                _lib.call("cc_gmm_em_step", Xb.data_ptr(), *shape, float(tol), float(reg_covar), int(max_iter),
+                _lib.call(em_step, Xb.data_ptr(), *shape, float(tol), float(reg_covar), int(max_iter),
                           ws.data_ptr(), ws.numel(), st)
                 _lib.call("cc_gmm_active", ws.data_ptr(), ctypes.addressof(active), ctypes.addressof(failed), st)
                 iterations += 1
@@ -920,7 +955,7 @@ def gmm_batch(X64: torch.Tensor, rows: torch.Tensor, cols_b, Ks, h_begin: int, l
         if failed.value:
             raise IllDefinedMixture()
         with timed("cc_gmm_finish"):
-            _lib.call("cc_gmm_finish", Xb.data_ptr(), rows.data_ptr(), *shape, int(init > 0), int(h_begin),
+            _lib.call(finish, Xb.data_ptr(), rows.data_ptr(), *shape, int(init > 0), int(h_begin),
                       labels.data_ptr(), labels.shape[1], labels.shape[2], _lib.ptr(lower_bound), _lib.ptr(n_iter),
                       _lib.ptr(converged), ldo, ws.data_ptr(), ws.numel(), st)
     return iterations
@@ -929,8 +964,9 @@ def gmm_batch(X64: torch.Tensor, rows: torch.Tensor, cols_b, Ks, h_begin: int, l
 def gmm_labels(X64: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, labels: torch.Tensor,
                budget: int = None, n_init: int = 1, seed: int = 0, tol: float = 1e-3, reg_covar: float = 1e-6,
                max_iter: int = 100, cols_d: torch.Tensor = None, lower_bound: torch.Tensor = None,
-               n_iter: torch.Tensor = None, converged: torch.Tensor = None) -> dict:
+               n_iter: torch.Tensor = None, converged: torch.Tensor = None, covariance: str = 'diag') -> dict:
     """Fill labels[k, idx[h, r], h] for h in [h0, h1) and every K of Ks with GMM(n_components=K, ...)
+    (covariance 'diag') or FullGMM(n_components=K, ...) ('full')
     over X64[idx[h]] (float64 [n, d], device), under feature subsampling over X64[idx[h]][:, cols[h]]
     (cols_d int32 [H, md], device, indexed by the global h like idx_d).  budget: device bytes for the
     batches (default: half the free memory); lower_bound / n_iter / converged: optional [nK, H]
@@ -944,7 +980,8 @@ def gmm_labels(X64: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, lab
     Ks = [int(K) for K in Ks]
     if budget is None:
         budget = torch.cuda.mem_get_info(dev)[0] // 2
-    B = gmm_plan(n, m, max(nh, 1), Ks, md, budget)
+    _gmm_entry(covariance, "start")
+    B = gmm_plan(n, m, max(nh, 1), Ks, md, budget, covariance)
     stats = dict(route='batched', batch=B, launches=0, em_iterations=0, inits=int(n_init))
     if cols_d is not None:
         stats['feature_subsampling'] = md
@@ -953,11 +990,12 @@ def gmm_labels(X64: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, lab
     if min(Ks) < 1 or max(Ks) > m:
         raise ValueError(f"every K must lie in [1, m = {m}], got {Ks}")
     Ks_h = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
-    ws = gmm_workspace(m, md, B, Ks_h, dev)
+    ws = gmm_workspace(m, md, B, Ks_h, dev, covariance)
     for a in range(h0, h1, B):
         b = min(a + B, h1)
         stats['em_iterations'] += gmm_batch(
             X64, idx_d[a:b].contiguous(), None if cols_d is None else cols_d[a:b].contiguous(), Ks, a, labels,
-            n_init, seed, tol, reg_covar, max_iter, lower_bound, n_iter, converged, ws=ws, budget=budget)
+            n_init, seed, tol, reg_covar, max_iter, lower_bound, n_iter, converged, ws=ws, budget=budget,
+            covariance=covariance)
         stats['launches'] += 1
     return stats

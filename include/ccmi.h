@@ -43,6 +43,10 @@
  *                         CC.py:282 for the GMM base clusterer (diagonal Gaussian mixture, sklearn's
  *                         GaussianMixture(covariance_type='diag') in float64): batched EM of every
  *                         (resample, K) problem from a k-means initialisation, best of n_init
+ *   cc_gmm_full_start, cc_gmm_full_em_step, cc_gmm_full_finish
+ *                         the same for FullGMM (full covariances, sklearn's default
+ *                         covariance_type='full'): weighted covariances, batched Cholesky and
+ *                         triangular inverse, the E-step against the precision factor
  */
 #ifndef CCMI_H
 #define CCMI_H
@@ -412,6 +416,41 @@ int cc_gmm_active(const void* workspace, int* active, int* failed, void* stream)
 int cc_gmm_finish(const double* Xb, const int* idx, int B, int m, int md, const int* Ks, int nK, int keep_best,
                   int h_begin, uint8_t* labels, int64_t n, int64_t ldl, double* lower_bound, int* n_iter,
                   uint8_t* converged, int64_t ldo, void* workspace, size_t ws_bytes, void* stream);
+
+/* FullGMM: the same EM for full covariances (sklearn 1.7's GaussianMixture(covariance_type='full')
+ * in float64, restated in gmm.py's FullGMM).  The batch, the rows (cc_gmm_gather), Ks, the
+ * workspace header and the sequence of calls are the diagonal model's, with the limits
+ * 1 <= Ks[k] <= min(m, 127), nK <= 127, B * nK <= 65535 and 1 <= md <= 128.  The M-step is the
+ * means (resp^T [x, 1]), the lower triangle of every component's weighted covariance of the
+ * centred rows (sklearn's dot(resp_c * diff.T, diff) / nk_c with reg_covar on the diagonal), and
+ * per component its Cholesky factor L, the precision factor P = L^-T, mu P and the log
+ * determinant; the E-step is sum_j ((x P)_j - (mu P)_j)^2 on the float64 matrix cores.  Every sum
+ * has a fixed order (csrc/gmm_full.hip), none depends on the grid or the batch, and there is no
+ * floating-point atomic.  A pivot of the factorisation that is not positive marks the problem
+ * failed.
+ *
+ * cc_gmm_full_workspace_bytes: the workspace of the three calls below (0 for arguments they
+ * refuse); per problem the responsibilities (8 m Kp bytes), the M-step sums and the means
+ * (8 Kp (2 md + 1)), the factors (8 K md md), mu P (8 Kp md), three constants per component and
+ * the 16-row tile sums.  cc_gmm_active reads this workspace as it reads cc_gmm_start's. */
+size_t cc_gmm_full_workspace_bytes(int m, int md, int B, const int* Ks, int nK);
+
+/* cc_gmm_start for full covariances: the one-hot responsibilities, sklearn's _initialize and the
+ * state.  Arguments as cc_gmm_start's. */
+int cc_gmm_full_start(const double* Xb, const int* idx, int B, int m, int md, const int* Ks, int nK,
+                      const uint8_t* init_labels, int64_t n, int64_t ldl, int col_begin, double reg_covar,
+                      void* workspace, size_t ws_bytes, void* stream);
+
+/* cc_gmm_em_step for full covariances: one E-step, the decision and the M-step of every problem
+ * still active.  Arguments as cc_gmm_em_step's; cc_gmm_active then reads the counts. */
+int cc_gmm_full_em_step(const double* Xb, int B, int m, int md, const int* Ks, int nK, double tol, double reg_covar,
+                        int max_iter, void* workspace, size_t ws_bytes, void* stream);
+
+/* cc_gmm_finish for full covariances: which problems this init wins, their scalar outputs and
+ * the labels of a final E-step.  Arguments as cc_gmm_finish's. */
+int cc_gmm_full_finish(const double* Xb, const int* idx, int B, int m, int md, const int* Ks, int nK, int keep_best,
+                       int h_begin, uint8_t* labels, int64_t n, int64_t ldl, double* lower_bound, int* n_iter,
+                       uint8_t* converged, int64_t ldo, void* workspace, size_t ws_bytes, void* stream);
 
 /* Batched k-means for every (resample h, K, init) problem, replacing the per-(K, h)
  * clusterer.fit_predict(X[indices]) of CC.py:282 for the default clusterer

@@ -2,7 +2,7 @@
 tools/features_f64_time.py: n = 10 000, d = 64 blobs (float64), subsampling 0.8 (m = 8000),
 K = 2..15, H = 64, n_init 1 and 3.
 
-    python tools/gmm_device_time.py [OUT.txt] [--fits 3] [--no-host] [--small]
+    python tools/gmm_device_time.py [OUT.txt] [--fits 3] [--no-host] [--small] [--full]
 
 Per n_init: one warm-up fit, then `fits` timed fits of ConsensusClustering(clusterer=GMM()): the
 clustering stage (`timings_['cluster']`, a wall clock between synchronisations) and HIP events
@@ -11,7 +11,9 @@ on the host, once each: the 16-worker host loop of the same GMM (a subclass, so 
 'host-clusterer') and of sklearn's GaussianMixture(covariance_type='diag'), both on the same
 resamples; the host GMM fit's pair counts are compared with the device fit's.  Prints every line
 and, with a file argument, also writes it to that file.  --small: a toy shape to rehearse the
-script."""
+script.  --full: the full-covariance model (FullGMM) against its own host loop and
+sklearn's GaussianMixture(covariance_type='full'); where the pair counts differ, the problems
+whose labels differ are listed with the device's and a host refit's n_iter and lower bound."""
 import argparse
 import os
 import statistics
@@ -26,13 +28,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sklearn.datasets import make_blobs  # noqa: E402
 from sklearn.mixture import GaussianMixture  # noqa: E402
 
-from consensus_clustering_amd import GMM, ConsensusClustering, engine  # noqa: E402
+from consensus_clustering_amd import GMM, ConsensusClustering, FullGMM, engine  # noqa: E402
 
 _p = argparse.ArgumentParser()
 _p.add_argument("out", nargs="?")
 _p.add_argument("--fits", type=int, default=3)
 _p.add_argument("--no-host", action="store_true")
 _p.add_argument("--small", action="store_true")
+_p.add_argument("--full", action="store_true")
 OPT = _p.parse_args()
 OUT = open(OPT.out, "w") if OPT.out else None
 N, D_, H = (600, 16, 8) if OPT.small else (10_000, 64, 64)
@@ -41,6 +44,33 @@ Ks = list(range(2, 16))
 
 class HostGMM(GMM):
     """A subclass: the host loop."""
+
+
+class HostFullGMM(FullGMM):
+    """A subclass: the host loop."""
+
+
+COV = 'full' if OPT.full else 'diag'
+DEV, HOST = (FullGMM, HostFullGMM) if OPT.full else (GMM, HostGMM)
+
+
+def differing(dev, host, X, n_init, limit=8, also=()):
+    """The (K, h) problems whose labels differ between the device fit and a host fit, and for the
+    first `limit` the device's n_iter and bound next to a host refit's (the device fit's seed,
+    rows and columns).  also: (k, h) problems listed whether they differ or not; the --small
+    rehearsal passes one, so that this report runs even though nothing differs."""
+    a, b = dev.labels_.cpu().numpy(), host.labels_.cpu().numpy()
+    idx, cols = dev.resampling_indices_, dev.feature_indices_
+    where = [(k, h) for k in range(len(Ks)) for h in range(H) if not np.array_equal(a[k, :, h], b[k, :, h])]
+    say(f"   labels differ in {len(where)} of {len(Ks) * H} problems: (K, h) {[(Ks[k], h) for k, h in where]}")
+    for k, h in (list(also) + where)[:limit]:
+        rows = X[idx[h]] if cols is None else X[idx[h]][:, cols[h]]
+        ref = DEV(n_components=Ks[k], n_init=n_init, random_state=dev.random_state).fit(rows)
+        nd = int((a[k, idx[h], h] != b[k, idx[h], h]).sum())
+        lb = float(dev.gmm_lower_bound_[k, h])
+        say(f"   K={Ks[k]} h={h}: {nd} of {idx.shape[1]} rows differ; device n_iter {int(dev.gmm_n_iter_[k, h])} "
+            f"bound {lb!r}; host n_iter {ref.n_iter_} bound {ref.lower_bound_!r} (relative difference "
+            f"{abs(lb - ref.lower_bound_) / abs(ref.lower_bound_):.2e}, tol 1e-3 on the bound's change)")
 
 
 def say(*a):
@@ -74,17 +104,17 @@ def main():
     X = X.astype(np.float32).astype(np.float64)
     m = int(0.8 * N)
     say(f"== float64 C2-like: n={N} d={D_} {X.dtype} blobs, subsampling 0.8 (m={m}), K={Ks[0]}..{Ks[-1]}, H={H}, "
-        f"GMM (diag, tol 1e-3, max_iter 100); {torch.cuda.get_device_name()}")
+        f"{DEV.__name__} ({COV}, tol 1e-3, max_iter 100); {torch.cuda.get_device_name()}")
     for n_init in (1, 3):
-        cc, _ = fit(X, GMM(), n_init)  # warm-up
-        assert cc.backend_ == "gpu-gmm"
+        cc, _ = fit(X, DEV(), n_init)  # warm-up
+        assert cc.backend_ == "gpu-gmm" and cc.gmm_covariance_type_ == COV
         say(f"-- n_init={n_init}: plan {cc.gmm_stats_}; EM iterations per problem (winning init): max "
             f"{int(cc.gmm_n_iter_.max())}, mean {float(cc.gmm_n_iter_.float().mean()):.2f}; converged "
             f"{int(cc.gmm_converged_.sum())} of {cc.gmm_converged_.numel()}")
         wall, stages, kern = [], {}, {}
         for _ in range(OPT.fits):
             engine.TIMERS = {}
-            cc, w = fit(X, GMM(), n_init)
+            cc, w = fit(X, DEV(), n_init)
             summary = engine.timer_summary(engine.TIMERS)
             engine.TIMERS = None
             wall.append(w)
@@ -98,20 +128,24 @@ def main():
         if OPT.no_host:
             continue
         dev_s = statistics.median(stages['cluster']) / 1e3
-        host, w = fit(X, HostGMM(), n_init, n_jobs=16)
+        host, w = fit(X, HOST(), n_init, n_jobs=16)
         assert host.backend_ == "host-clusterer"
         same = all(np.array_equal(cc.pair_counts_[K], host.pair_counts_[K]) for K in Ks)
         host_s = host.timings_['cluster']
-        say(f"host GMM (gmm.py), 16 workers: cluster stage {host_s:.2f} s, {H * len(Ks) / host_s:.0f} resample-fits/s; "
+        say(f"host {DEV.__name__} (gmm.py), 16 workers: cluster stage {host_s:.2f} s, {H * len(Ks) / host_s:.0f} resample-fits/s; "
             f"pair counts identical to the device fit's: {same}")
-        sk, w = fit(X, GaussianMixture(covariance_type='diag'), n_init, n_jobs=16)
+        if not same or OPT.small:
+            differing(cc, host, X, n_init, also=[(len(Ks) - 1, H - 1)] if OPT.small else ())
+        sk, w = fit(X, GaussianMixture(covariance_type=COV), n_init, n_jobs=16)
         assert sk.backend_ == "host-clusterer"
         sk_s = sk.timings_['cluster']
         same_sk = all(np.array_equal(cc.pair_counts_[K], sk.pair_counts_[K]) for K in Ks)
-        say(f"sklearn GaussianMixture('diag'), 16 workers: cluster stage {sk_s:.2f} s, {H * len(Ks) / sk_s:.0f} "
+        say(f"sklearn GaussianMixture('{COV}'), 16 workers: cluster stage {sk_s:.2f} s, {H * len(Ks) / sk_s:.0f} "
             f"resample-fits/s; pair counts identical to the device fit's: {same_sk}")
+        if not same_sk:
+            differing(cc, sk, X, n_init, limit=0)
         say(f"device cluster stage {dev_s:.3f} s, {H * len(Ks) / dev_s:.0f} resample-fits/s: {host_s / dev_s:.1f}x the "
-            f"16-worker host GMM, {sk_s / dev_s:.1f}x the 16-worker sklearn loop (host runs measured once)")
+            f"16-worker host {DEV.__name__}, {sk_s / dev_s:.1f}x the 16-worker sklearn loop (host runs measured once)")
 
 
 if __name__ == "__main__":
