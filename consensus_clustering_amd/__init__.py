@@ -5,6 +5,7 @@ __version__ = "0.1.0"
 
 from .pam import PAM  # noqa: F401
 from .gmm import GMM, FullGMM  # noqa: F401
+from .nmf import NMF  # noqa: F401
 from .post import best_k, cdf_area, cdf_from_counts, delta_k  # noqa: F401
 
 

@@ -94,6 +94,12 @@ SIGNATURES = {
                                      _vp]),
     "cc_gmm_full_finish": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_i64, _c_i64,
                                     _vp, _vp, _vp, _c_i64, _vp, _c_sz, _vp]),
+    "cc_nmf_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int, _vp, _c_int]),
+    "cc_nmf_start": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _c_sz, _vp]),
+    "cc_nmf_steps": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_dbl, _c_int, _vp, _c_sz,
+                              _vp]),
+    "cc_nmf_finish": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_i64, _c_i64,
+                               _vp, _vp, _vp, _c_i64, _vp, _c_sz, _vp]),
     "cc_kmeans_f64_workspace_bytes": (_c_sz, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int]),
     "cc_kmeans_f64": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp,
                                _c_int, _c_int, _c_int, _c_dbl, _vp, _c_int, _vp, _vp, _c_int, _vp,

@@ -26,7 +26,11 @@ What runs where (``fit``):
                   float64; gmm_covariance_type_ tells which) -> batched EM of
                   every (resample, K), each init started from the float64 k-means engine's labels
                   (cc_gmm_gather, cc_gmm_start, cc_gmm_em_step, cc_gmm_finish; FullGMM:
-                  cc_gmm_full_start, cc_gmm_full_em_step, cc_gmm_full_finish, at most 128 features)
+                  cc_gmm_full_start, cc_gmm_full_em_step, cc_gmm_full_finish, at most 128 features);
+                  NMF (nmf.py, sklearn's NMF(init='random', solver='mu') in float64) -> batched
+                  multiplicative updates of every (resample, K), each init from normals drawn on
+                  the host and shared by the resamples (cc_gmm_gather, cc_nmf_start, cc_nmf_steps,
+                  cc_nmf_finish)
   I, M, histogram int8-MFMA tiles of the upper triangle (cc_cosample / cc_coassoc)
   hist/cdf/PAC    host float64 from 20 exact integer counts (post.py)
   multi-GPU       resamples and triangle tiles sharded over torch.distributed ranks
@@ -59,6 +63,7 @@ from .pam import METRICS as HC_METRICS  # sklearn's metric spellings -> scipy's 
 from .pam import PAM, degenerate_rows as _hc_degenerate, refuse_not_finite
 from .pam import validate as _pam_validate
 from .gmm import GMM, FullGMM, validate as _gmm_validate
+from .nmf import NEGATIVE as _NMF_NEGATIVE, NMF, validate as _nmf_validate
 
 KMAX = 127  # largest K: uint8 labels (0xFF = not sampled) and int8 one-hot channels
 
@@ -261,6 +266,25 @@ def _gmm_params(p):
                 reg_covar=float(p["reg_covar"]))
 
 
+def _nmf_spec(est):
+    """The parameters of an NMF that the device reproduces (cc_nmf_start, cc_nmf_steps,
+    cc_nmf_finish), else None: exactly that type (a subclass may override anything), integer
+    max_iter >= 1 and n_init >= 1, finite tol >= 0."""
+    if type(est) is not NMF:
+        return None
+    p = est.get_params()
+    for name in ("max_iter", "n_init"):
+        v = p.get(name)
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+            return None
+    v = p.get("tol")
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        return None
+    if not (np.isfinite(v) and v >= 0):
+        return None
+    return dict(n_init=int(p["n_init"]), max_iter=int(p["max_iter"]), tol=float(p["tol"]))
+
+
 class ConsensusClustering:
     """Monti consensus clustering on MI355X.  Drop-in for CC.py:11."""
 
@@ -402,6 +426,7 @@ class ConsensusClustering:
         self.pam_stats_ = self.pam_metric_ = self.pam_inertia_ = self.pam_n_iter_ = None
         self.gmm_stats_ = self.gmm_lower_bound_ = self.gmm_n_iter_ = self.gmm_converged_ = None
         self.gmm_covariance_type_ = None
+        self.nmf_stats_ = self.nmf_reconstruction_err_ = self.nmf_n_iter_ = self.nmf_converged_ = None
         if self.hierarchical not in ('auto', 'device', 'host'):
             raise ValueError("hierarchical must be 'auto', 'device' or 'host'")
         self.partial_ = False
@@ -485,9 +510,12 @@ class ConsensusClustering:
                                   f"{md} features the fits run on the host (one fit per resample and K)", UserWarning)
                     gmm = None
                 self.gmm_covariance_type_ = 'full' if gmm is not None else None
+        nmf = None
+        if Ks and km is None and hc is None and pam is None and gmm is None:
+            nmf = _nmf_spec(self.clusterer)
         self.backend_ = ('gpu-kmeans' if km is not None else 'gpu-hc' if hc is not None
                          else 'gpu-pam' if pam is not None else 'gpu-gmm' if gmm is not None
-                         else 'host-clusterer')
+                         else 'gpu-nmf' if nmf is not None else 'host-clusterer')
         precision = self.precision
         if precision == 'auto':
             # the reference's clusterer computes in X's dtype (CC.py:282): float64 input keeps
@@ -534,6 +562,8 @@ class ConsensusClustering:
             self.gmm_n_iter_ = torch.zeros((len(Ks), H), dtype=torch.int32, device=dev)
             self.gmm_converged_ = torch.zeros((len(Ks), H), dtype=torch.uint8, device=dev)
             self.gmm_stats_ = self._fit_gmm(X, wdtype, gmm, idx_d, n, m, h0, h1, Ks, labels, dev, cols=cols)
+        elif Ks and nmf is not None:
+            self.nmf_stats_ = self._fit_nmf(X, wdtype, nmf, idx_d, n, m, h0, h1, Ks, labels, dev, cols=cols)
         elif Ks:
             if isinstance(X, torch.Tensor):
                 X = X.cpu().numpy()
@@ -677,6 +707,39 @@ class ConsensusClustering:
         if dist.first_failure(code, dev) is not None:
             raise engine.IllDefinedMixture()
         return stats
+
+    def _fit_nmf(self, X, wdtype, spec, idx_d, n, m, h0, h1, Ks, labels, dev, cols=None):
+        """CC.py:282 for NMF(**spec) on the device: the refusals from host values on every rank
+        before any launch (X that is not finite or holds a negative entry; a device tensor is
+        tested with torch), the plan when a workspace_budget is set (too small: raises before any
+        launch), X as float64 on the device (a float32 X is cast, with a warning: NMF computes in
+        float64) and the column list, then the multiplicative updates of every (resample, K) of
+        [h0, h1) into this rank's columns of the label matrix, of nmf_reconstruction_err_,
+        nmf_n_iter_ and nmf_converged_ (engine.nmf_labels).  No problem can fail."""
+        if isinstance(X, torch.Tensor):
+            if not bool(torch.isfinite(X).all()):
+                refuse_not_finite(X.detach().cpu().numpy())
+            if X.numel() and bool((X < 0).any()):
+                raise ValueError(_NMF_NEGATIVE)
+        else:
+            _nmf_validate(X)
+        md = X.shape[1] if cols is None else cols.shape[1]
+        if self.workspace_budget is not None:
+            engine.nmf_plan(n, m, max(h1 - h0, 1), Ks, md, self.workspace_budget, spec["n_init"])
+        if np.dtype(wdtype) != np.float64:
+            warnings.warn("NMF computes in float64: the float32 X is cast to float64 (sklearn's NMF would compute "
+                          "in float32)", UserWarning)
+        H = idx_d.shape[0]
+        self.nmf_reconstruction_err_ = torch.zeros((len(Ks), H), dtype=torch.float64, device=dev)
+        self.nmf_n_iter_ = torch.zeros((len(Ks), H), dtype=torch.int32, device=dev)
+        self.nmf_converged_ = torch.zeros((len(Ks), H), dtype=torch.uint8, device=dev)
+        X64 = (X.to(dev, torch.float64) if isinstance(X, torch.Tensor)
+               else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(dev)).contiguous()
+        cols_d = None if cols is None else torch.from_numpy(cols).to(dev)
+        return engine.nmf_labels(X64, idx_d, h0, h1, Ks, labels, budget=self.workspace_budget,
+                                 seed=int(self.random_state), cols_d=cols_d,
+                                 reconstruction_err=self.nmf_reconstruction_err_, n_iter=self.nmf_n_iter_,
+                                 converged=self.nmf_converged_, **spec)
 
     def _fit_on_distances(self, X, wdtype, metric, n, m, Ks, dev, cols, validate, plan, run):
         """What the device clusterers over pdist(X, metric) share (the trees and PAM): the

@@ -999,3 +999,176 @@ def gmm_labels(X64: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, lab
             covariance=covariance)
         stats['launches'] += 1
     return stats
+
+
+# ---------------------------------------------------------------- NMF base clusterer
+
+def nmf_bytes(m: int, md: int, Ks) -> int:
+    """Device bytes one resample of an NMF batch needs: its compact float64 rows [m, md], its row and
+    column indices and per K (Kp = K rounded up to 16) W [m, Kp], H and W^T X [Kp, md] each, H H^T
+    and W^T W [Kp, Kp] each, the 16-row tile sums of the error and the problem's 48-byte state:
+    cc_nmf_workspace_bytes plus the rows."""
+    m, md = int(m), int(md)
+    per = 8 * m * md + 4 * m + 4 * md
+    for K in Ks:
+        Kp = (int(K) + 15) & ~15
+        per += _up256(8 * (m * Kp + 2 * Kp * md + 2 * Kp * Kp + (m + 15) // 16)) + 64
+    return per
+
+
+def nmf_plan(n: int, m: int, nh: int, Ks, md: int, budget: int, n_init: int = 1) -> int:
+    """B = the resamples per batch for the nh resamples of a rank: as many as fit the budget next
+    to the normals of every init (float64, (m + md) * sum(Ks) values an init, shared by the
+    resamples), at most nh and at most 65535 problems a launch.  Raises when one resample does not
+    fit."""
+    nK = max(len(Ks), 1)
+    per = nmf_bytes(m, md, Ks)
+    fixed = 1024 + 8 * int(n_init) * (int(m) + int(md)) * sum(int(K) for K in Ks)
+    fit = (int(budget) - fixed) // per
+    if fit < 1:
+        raise ValueError(
+            f"workspace_budget = {int(budget)} bytes cannot hold the NMF clusterer: one resample "
+            f"of m = {int(m)} over {int(md)} features ({per + fixed} bytes) is needed")
+    return max(1, min(int(nh), int(fit), 65535 // nK))
+
+
+def nmf_workspace(m: int, md: int, B: int, Ks_h: np.ndarray, device) -> torch.Tensor:
+    nbytes = int(_lib.load().cc_nmf_workspace_bytes(int(m), int(md), int(B), Ks_h.ctypes.data, len(Ks_h)))
+    if nbytes == 0:
+        raise ValueError(f"NMF on the device needs 1 <= K <= 127, at most 127 values of K and at most 65535 problems "
+                         f"a batch, got m = {m}, md = {md}, B = {B}, Ks = {Ks_h.tolist()}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def nmf_normals(seed: int, m: int, md: int, Ks, n_init: int, device):
+    """The absolute normals of every init on the device: per K one RandomState(seed) and per init
+    |N_H| [K, md] drawn first, then |N_W| [m, K] (nmf.init_normals).  Returns (W, H): float64
+    [n_init, m * sum(Ks)] and [n_init, md * sum(Ks)], the values of each K concatenated."""
+    from .nmf import init_normals
+
+    Ws = [[] for _ in range(int(n_init))]
+    Hs = [[] for _ in range(int(n_init))]
+    for K in Ks:
+        rs = np.random.RandomState(seed)
+        for i in range(int(n_init)):
+            W, H = init_normals(rs, int(m), int(md), int(K))
+            Ws[i].append(W.ravel())
+            Hs[i].append(H.ravel())
+    W = torch.from_numpy(np.stack([np.concatenate(w) for w in Ws])).to(device)
+    H = torch.from_numpy(np.stack([np.concatenate(h) for h in Hs])).to(device)
+    return W.contiguous(), H.contiguous()
+
+
+NMF_TEST_EVERY = 10  # sklearn's stopping test runs at the iterations that are multiples of 10
+
+
+def nmf_batch(X64: torch.Tensor, rows: torch.Tensor, cols_b, Ks, h_begin: int, labels: torch.Tensor, normals,
+              tol: float = 1e-4, max_iter: int = 200, reconstruction_err: torch.Tensor = None,
+              n_iter: torch.Tensor = None, converged: torch.Tensor = None, ws: torch.Tensor = None) -> int:
+    """NMF(n_components=K, n_init, tol, max_iter) of every (resample b of rows [B, m], K) over
+    X64[rows[b]][:, cols_b[b]] (cols_b None: all columns) from normals = nmf_normals(...), whose
+    first extent is n_init: cc_gmm_gather, then per init cc_nmf_start, cc_nmf_steps ten iterations a
+    call until cc_gmm_active reads 0 (one synchronisation per stopping test), and cc_nmf_finish
+    into labels[k, rows[b, r], h_begin + b] (uint8 [nK, n, Hpad]) and reconstruction_err / n_iter /
+    converged ([nK, H], at column h_begin + b) where the init is the best so far.  Returns the
+    iterations launched."""
+    assert X64.dtype == torch.float64 and X64.dim() == 2 and X64.is_contiguous() and X64.is_cuda
+    assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.is_contiguous()
+    n, d = X64.shape
+    B, m = rows.shape
+    dev = X64.device
+    md = d if cols_b is None else cols_b.shape[1]
+    Ks_h = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
+    nK = len(Ks_h)
+    assert labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous() and labels.shape[0] == nK
+    NW, NH = normals
+    sumK = int(Ks_h.sum())
+    for t, width in ((NW, m * sumK), (NH, md * sumK)):
+        assert t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == width and t.is_contiguous() and t.is_cuda
+    ldo = 0
+    for t, dt in ((reconstruction_err, torch.float64), (n_iter, torch.int32), (converged, torch.uint8)):
+        if t is not None:
+            assert t.dtype == dt and t.dim() == 2 and t.shape[0] == nK and t.is_contiguous()
+            assert ldo in (0, t.shape[1])
+            ldo = t.shape[1]
+    # an entry outside its range would be read out of bounds by the gather: checked here, on the
+    # device tensors, before anything is launched
+    lo, hi = (int(v) for v in torch.aminmax(rows))
+    if lo < 0 or hi >= n:
+        raise ValueError(f"idx entries must lie in [0, {n}), got [{lo}, {hi}]")
+    if cols_b is not None:
+        assert cols_b.dtype == torch.int32 and cols_b.dim() == 2 and cols_b.shape[0] == B and cols_b.is_contiguous()
+        lo, hi = (int(v) for v in torch.aminmax(cols_b))
+        if lo < 0 or hi >= d:
+            raise ValueError(f"cols entries must lie in [0, {d}), got [{lo}, {hi}]")
+    if ws is None:
+        ws = nmf_workspace(m, md, B, Ks_h, dev)
+    st = stream_ptr(dev)
+    Xb = torch.empty((B, m, md), dtype=torch.float64, device=dev)
+    with timed("cc_gmm_gather"):
+        _lib.call("cc_gmm_gather", X64.data_ptr(), n, d, rows.data_ptr(), _lib.ptr(cols_b), B, m, md, Xb.data_ptr(), st)
+    shape = (B, m, md, Ks_h.ctypes.data, nK)
+    iterations = 0
+    active, failed = ctypes.c_int(0), ctypes.c_int(0)
+    max_iter = int(max_iter)
+    for init in range(NW.shape[0]):
+        with timed("cc_nmf_start"):
+            _lib.call("cc_nmf_start", Xb.data_ptr(), *shape, NW[init].data_ptr(), NH[init].data_ptr(), ws.data_ptr(),
+                      ws.numel(), st)
+        with timed("cc_nmf_steps"):
+            first = 1
+            while first <= max_iter:
+                # up to the next stopping test, or to max_iter where there is none (tol = 0)
+                count = min(NMF_TEST_EVERY, max_iter - first + 1) if tol > 0 else max_iter - first + 1
+                _lib.call("cc_nmf_steps", Xb.data_ptr(), *shape, first, count, float(tol), max_iter, ws.data_ptr(),
+                          ws.numel(), st)
+                first += count
+                iterations += count
+                _lib.call("cc_gmm_active", ws.data_ptr(), ctypes.addressof(active), ctypes.addressof(failed), st)
+                if active.value == 0:
+                    break
+        with timed("cc_nmf_finish"):
+            _lib.call("cc_nmf_finish", Xb.data_ptr(), rows.data_ptr(), *shape, int(init > 0), int(h_begin),
+                      labels.data_ptr(), labels.shape[1], labels.shape[2], _lib.ptr(reconstruction_err),
+                      _lib.ptr(n_iter), _lib.ptr(converged), ldo, ws.data_ptr(), ws.numel(), st)
+    return iterations
+
+
+def nmf_labels(X64: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, labels: torch.Tensor,
+               budget: int = None, n_init: int = 1, seed: int = 0, tol: float = 1e-4, max_iter: int = 200,
+               cols_d: torch.Tensor = None, reconstruction_err: torch.Tensor = None, n_iter: torch.Tensor = None,
+               converged: torch.Tensor = None) -> dict:
+    """Fill labels[k, idx[h, r], h] for h in [h0, h1) and every K of Ks with NMF(n_components=K,
+    n_init, random_state=seed, tol, max_iter) over X64[idx[h]] (float64 [n, d], non-negative, device),
+    under feature subsampling over X64[idx[h]][:, cols[h]] (cols_d int32 [H, md], device, indexed by
+    the global h like idx_d).  The normals come from numpy on the host and are uploaded once per
+    call.  budget: device bytes for the batches (default: half the free memory);
+    reconstruction_err / n_iter / converged: optional [nK, H] device tensors filled at the columns
+    [h0, h1).  Returns dict(route='batched', batch, launches, iterations, inits)."""
+    n, d = X64.shape
+    dev = X64.device
+    m = idx_d.shape[1]
+    md = d if cols_d is None else cols_d.shape[1]
+    nh = h1 - h0
+    Ks = [int(K) for K in Ks]
+    if budget is None:
+        budget = torch.cuda.mem_get_info(dev)[0] // 2
+    B = nmf_plan(n, m, max(nh, 1), Ks, md, budget, n_init)
+    stats = dict(route='batched', batch=B, launches=0, iterations=0, inits=int(n_init))
+    if cols_d is not None:
+        stats['feature_subsampling'] = md
+    if nh <= 0 or not Ks:
+        return stats
+    if min(Ks) < 1 or max(Ks) > 127:
+        raise ValueError(f"every K must lie in [1, 127], got {Ks}")
+    Ks_h = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
+    ws = nmf_workspace(m, md, B, Ks_h, dev)
+    with timed("nmf_normals"):
+        normals = nmf_normals(int(seed), m, md, Ks, n_init, dev)
+    for a in range(h0, h1, B):
+        b = min(a + B, h1)
+        stats['iterations'] += nmf_batch(
+            X64, idx_d[a:b].contiguous(), None if cols_d is None else cols_d[a:b].contiguous(), Ks, a, labels,
+            normals, tol, max_iter, reconstruction_err, n_iter, converged, ws=ws)
+        stats['launches'] += 1
+    return stats

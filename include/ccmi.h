@@ -47,6 +47,10 @@
  *                         the same for FullGMM (full covariances, sklearn's default
  *                         covariance_type='full'): weighted covariances, batched Cholesky and
  *                         triangular inverse, the E-step against the precision factor
+ *   cc_nmf_start, cc_nmf_steps, cc_nmf_finish
+ *                         CC.py:282 for the NMF base clusterer (sklearn's NMF(init='random',
+ *                         solver='mu') in float64): batched multiplicative updates of every
+ *                         (resample, K) problem, best of n_init
  */
 #ifndef CCMI_H
 #define CCMI_H
@@ -451,6 +455,48 @@ int cc_gmm_full_em_step(const double* Xb, int B, int m, int md, const int* Ks, i
 int cc_gmm_full_finish(const double* Xb, const int* idx, int B, int m, int md, const int* Ks, int nK, int keep_best,
                        int h_begin, uint8_t* labels, int64_t n, int64_t ldl, double* lower_bound, int* n_iter,
                        uint8_t* converged, int64_t ldo, void* workspace, size_t ws_bytes, void* stream);
+
+/* NMF: X ~ W H by multiplicative updates under the Frobenius loss (sklearn 1.7's NMF(init='random',
+ * solver='mu', beta_loss='frobenius') without regularisation in float64, restated in nmf.py) on
+ * each of B resamples' rows Xb [B][m][md] (float64, finite, non-negative, the batch cc_gmm_gather
+ * makes).  Problem (b, k) has Ks[k] components; the limits are m >= 1, md >= 1, 1 <= Ks[k] <= 127
+ * (K may exceed m and md), nK <= 127 and B * nK <= 65535.  Every contraction runs on the float64
+ * matrix cores in a fixed order (csrc/nmf.hip); no sum depends on the grid or the batch and there
+ * is no floating-point atomic, so a problem's results do not depend on the batch it ran in.  The
+ * device always forms (W^T W) H where sklearn's multi_dot may pick W^T (W H).
+ *
+ * cc_nmf_workspace_bytes: the workspace of the calls below (0 for arguments they refuse); per
+ * problem, with Kp = K rounded up to 16, W (8 m Kp bytes), H and W^T X (8 Kp md each), H H^T and
+ * W^T W (8 Kp Kp each), the 16-row tile sums of the error and the 48-byte state.  The workspace
+ * keeps each problem's best error across the inits of one batch, so one workspace serves every
+ * init: cc_nmf_start, cc_nmf_steps until cc_gmm_active reads 0, cc_nmf_finish. */
+size_t cc_nmf_workspace_bytes(int m, int md, int B, const int* Ks, int nK);
+
+/* Starts one init of every problem: avg_b = sqrt(mean(Xb[b]) / K) from a fixed-order mean,
+ * W = avg |N_W|, H = avg |N_H| and the error at init.  normals_w holds |N_W| [m][K] for every K of
+ * Ks, concatenated, normals_h |N_H| [K][md] likewise (float64, device); all B resamples share
+ * them.  Every problem is active afterwards. */
+int cc_nmf_start(const double* Xb, int B, int m, int md, const int* Ks, int nK, const double* normals_w,
+                 const double* normals_h, void* workspace, size_t ws_bytes, void* stream);
+
+/* Enqueues the iterations first .. first + count - 1 (1-based since cc_nmf_start, cut at max_iter)
+ * of every problem still active; an inactive problem costs no work.  After an iteration that is a
+ * multiple of 10 (when tol > 0) the error is evaluated and a problem stops, converged, when
+ * (previous error - error) / error at init < tol; after iteration max_iter every problem stops.
+ * After such an iteration the number of problems still active is left in the workspace for
+ * cc_gmm_active, which reads this workspace as it reads cc_gmm_start's (no problem fails). */
+int cc_nmf_steps(const double* Xb, int B, int m, int md, const int* Ks, int nK, int first, int count, double tol,
+                 int max_iter, void* workspace, size_t ws_bytes, void* stream);
+
+/* The results of one init: the final error sqrt(sum (X - W H)^2) of every problem; with
+ * keep_best = 0 (the first init) every problem wins, else those whose error is strictly smaller
+ * than the best of the inits before.  For the winners labels[k][idx[b][r]][h_begin + b] =
+ * argmax_c W[r][c] sqrt(sum_j H[c][j]^2) (first index on ties); labels uint8 [nK][n][ldl].
+ * reconstruction_err [nK][ldo] float64, n_iter [nK][ldo] int32 and converged [nK][ldo] uint8 (each
+ * may be NULL) receive the init's values at [k][h_begin + b]. */
+int cc_nmf_finish(const double* Xb, const int* idx, int B, int m, int md, const int* Ks, int nK, int keep_best,
+                  int h_begin, uint8_t* labels, int64_t n, int64_t ldl, double* reconstruction_err, int* n_iter,
+                  uint8_t* converged, int64_t ldo, void* workspace, size_t ws_bytes, void* stream);
 
 /* Batched k-means for every (resample h, K, init) problem, replacing the per-(K, h)
  * clusterer.fit_predict(X[indices]) of CC.py:282 for the default clusterer
