@@ -37,6 +37,10 @@ SIGNATURES = {
                             _vp, _vp, _c_int, _vp]),
     "cc_item_consensus": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_i64, _vp, _vp,
                                    _c_int, _vp, _vp]),
+    "cc_agreement_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int]),
+    "cc_agreement_num_tiles": (_c_i64, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "cc_agreement_sums": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_i64,
+                                   _c_i64, _vp, _vp, _c_sz, _vp]),
     "cc_bin_table": (_c_int, [_c_int, _vp, _vp, _c_sz, _vp]),
     "cc_bin_table_bytes": (_c_sz, [_c_int]),
     "cc_bin_table_max_rows": (_c_int, []),

@@ -45,7 +45,9 @@ labels returned instead of added into a shared Mij, so nothing races; the defaul
 the GPU whatever n_jobs says).
 Additions: ``cdf_area_``, ``delta_k_``, ``pac_area_``, ``best_k_``, ``predict`` and Monti's item and
 cluster consensus (``consensus_sums``, ``item_consensus``, ``cluster_consensus``, ``icl``), computed
-from the label matrix without the n x n matrices (cc_item_consensus).
+from the label matrix without the n x n matrices (cc_item_consensus); and the pairwise agreement
+of the resamples (``agreement_sums``, ``resample_agreement``, ``partition_agreement``,
+``stability``: adjusted Rand / Jaccard on the shared items, cc_agreement_sums).
 """
 from __future__ import annotations
 
@@ -971,6 +973,77 @@ class ConsensusClustering:
             out[K] = dict(consensus_labels=labels,
                           item_consensus=post.item_consensus_from_sums(S, labels, Kc),
                           cluster_consensus=post.cluster_consensus_from_sums(S, labels, Kc))
+        return out
+
+    # ------------------------------------------------------------------ resample agreement
+    def agreement_sums(self, K=None, labels=None):
+        """The exact contingency sums behind the agreement indices, as an int64 numpy array:
+        [H, H, 4] = (s0, s2, r2, c2) for every pair of the H = ``n_iterations`` resamples of K
+        (default ``best_k_``) over the items both drew, or, with ``labels`` (an int array of
+        length n with ids in [0, 126], as in ``consensus_sums``), [H, 4]: every resample against
+        that partition on the items the resample drew.  N[a][b] counts the shared items that the
+        first column puts in cluster a and the second in b; s0 = sum N, s2 = sum N^2,
+        r2 = sum_a (sum_b N)^2, c2 = sum_b (sum_a N)^2 (``post.agreement_from_sums``).  Computed
+        from the fitted label matrix ``labels_`` by cc_agreement_sums; no clustering is rerun.
+
+        Under a torch.distributed process group EVERY rank must call this method (and
+        ``resample_agreement`` / ``partition_agreement`` / ``stability``): rank r fills the pairs of
+        the tiles ``dist.shard(num_tiles, r, W)`` in a zeroed buffer and the int64 sums are
+        all-reduced (SUM), so every rank returns the one-rank result bit for bit."""
+        if labels is None:
+            if getattr(self, 'labels_', None) is None:
+                raise ValueError("fit() first")
+            K = self.best_k_ if K is None else K
+            if K not in self.cdf_at_K_data:
+                raise KeyError(f"K = {K} is not in K_range of the fit")
+        else:
+            K, labels, Kc = self._icl_args(K, labels)
+        k = list(self.cdf_at_K_data).index(K)
+        L = self.labels_[k]
+        n, H = self._N, int(self.n_iterations)
+        rank, W = dist.world()
+        if labels is None:
+            t0, t1 = dist.shard(engine.agreement_num_tiles(H, K), rank, W)
+            S = engine.agreement_sums(L, H, K, n, tile_begin=t0, tile_end=t1)
+        else:
+            col = torch.from_numpy(labels.astype(np.uint8)).to(L.device)
+            t0, t1 = dist.shard(engine.agreement_num_tiles(H, K, 1, Kc), rank, W)
+            S = engine.agreement_sums(L, H, K, n, col, 1, Kc, t0, t1)
+        dist.sum_counts(S)
+        S = S.cpu().numpy()
+        return S if labels is None else S[:, 0, :]
+
+    def resample_agreement(self, K=None, index='ari'):
+        """float64 [H, H]: the agreement of the clusterings of every two resamples of K (default
+        ``best_k_``) on the items both drew: ``index`` 'ari' (sklearn's adjusted_rand_score) or
+        'jaccard' (Ben-Hur, Elisseeff & Guyon 2002).  Symmetric, diagonal 1.0; NaN where two
+        resamples share fewer than two items."""
+        if index not in post.AGREEMENT_INDICES:
+            raise ValueError(f"index must be one of {post.AGREEMENT_INDICES}, got {index!r}")
+        return post.agreement_from_sums(self.agreement_sums(K), index)
+
+    def partition_agreement(self, K=None, labels=None, index='ari'):
+        """float64 [H]: how well each resample's clustering of K matches the partition ``labels``
+        (default ``predict(K)``, the consensus partition) on the items that resample drew; a low
+        entry marks an outlying resample.  ``labels`` as in ``agreement_sums``."""
+        if index not in post.AGREEMENT_INDICES:
+            raise ValueError(f"index must be one of {post.AGREEMENT_INDICES}, got {index!r}")
+        K, labels, _ = self._icl_args(K, labels)
+        return post.agreement_from_sums(self.agreement_sums(K, labels), index)
+
+    def stability(self, Ks=None, index='ari'):
+        """{K: mean agreement over the resample pairs h1 < h2} for every K of the fit (or the given
+        Ks), NaN entries (pairs sharing fewer than two items) left out; NaN when every entry is.
+        The stability criterion of Ben-Hur et al. (2002): a second opinion next to PAC and
+        delta-K that costs no extra clustering."""
+        if getattr(self, 'labels_', None) is None:
+            raise ValueError("fit() first")
+        iu = np.triu_indices(int(self.n_iterations), 1)
+        out = {}
+        for K in (list(self.cdf_at_K_data) if Ks is None else Ks):
+            vals = self.resample_agreement(K, index)[iu]
+            vals = vals[~np.isnan(vals)]
+            out[K] = float(vals.mean()) if vals.size else float('nan')
         return out
 
     @property

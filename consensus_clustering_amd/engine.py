@@ -308,6 +308,61 @@ def item_consensus_sums(labels_nh: torch.Tensor, n: int, Hpad: int, K: int, cl, 
     return S
 
 
+def agreement_num_tiles(HA: int, KA: int, HB: int = None, KB: int = None) -> int:
+    """Tiles of cc_agreement_sums for A against B (HB columns of KB clusters), or, with HB None,
+    for A with itself (the upper triangle of tiles)."""
+    sym = HB is None
+    return int(_lib.load().cc_agreement_num_tiles(int(HA), int(HA if sym else HB), int(KA),
+                                                  int(KA if sym else KB), int(sym)))
+
+
+def _label_columns(t: torch.Tensor, n: int, H: int, name: str):
+    """(tensor, row stride) of a [n, >= H] uint8 label view with unit column stride ([n] when H = 1)."""
+    if t.dim() == 1:
+        t = t.unsqueeze(1)
+    if (t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 2 or t.shape[0] != n or t.shape[1] < H
+            or (t.shape[1] > 1 and t.stride(1) != 1)):
+        raise ValueError(f"{name} must be a device uint8 [n, >= H] label view with unit column stride")
+    return t, (t.stride(0) if n > 1 else max(t.shape[1], 1))
+
+
+def agreement_sums(A_nh: torch.Tensor, HA: int, KA: int, n: int, B_nh: torch.Tensor = None, HB: int = None,
+                   KB: int = None, tile_begin: int = 0, tile_end: int = None, out: torch.Tensor = None) -> torch.Tensor:
+    """int64 [HA, HB, 4] on the device: (s0, s2, r2, c2) of the contingency table N of every pair
+    (column h1 of A_nh, column h2 of B_nh) over the items present in both: s0 = sum N,
+    s2 = sum N^2, r2 = sum_a (sum_b N)^2, c2 = sum_b (sum_a N)^2 (post.agreement_from_sums turns
+    them into the adjusted Rand or Jaccard index).  A_nh: uint8 [n, >= HA] (any row stride),
+    labels in [0, KA), any other byte = absent; B_nh likewise with HB, KB ([n] for one column),
+    or None: A with itself, [HA, HA, 4].  Only the pairs of tiles [tile_begin, tile_end)
+    (default: all of agreement_num_tiles) are written, with plain stores, into `out` when given
+    (contiguous int64 [HA, HB, 4]), else into zeros.  cc_agreement_sums on the current stream; the
+    scratch is the transposed columns, (HA + HB) rounded up to 128 each times n rounded up to 128 bytes."""
+    dev = A_nh.device
+    sym = B_nh is None
+    HA, KA, n = int(HA), int(KA), int(n)
+    HB, KB = (HA, KA) if sym else (int(HB), int(KB))
+    A_nh, ldA = _label_columns(A_nh, n, HA, "A_nh")
+    ldB = 0
+    if not sym:
+        B_nh, ldB = _label_columns(B_nh, n, HB, "B_nh")
+        if B_nh.device != dev:
+            raise ValueError("A_nh and B_nh must be on one device")
+    if out is None:
+        out = torch.zeros((max(HA, 0), max(HB, 0), 4), dtype=torch.int64, device=dev)
+    elif (out.dtype != torch.int64 or tuple(out.shape) != (HA, HB, 4) or not out.is_contiguous()
+          or out.device != dev):
+        raise ValueError("out must be a contiguous int64 [HA, HB, 4] tensor on the labels' device")
+    lib = _lib.load()
+    if tile_end is None:
+        tile_end = int(lib.cc_agreement_num_tiles(HA, HB, KA, KB, int(sym)))
+    ws = torch.empty(int(lib.cc_agreement_workspace_bytes(n, HA, 0 if sym else HB)), dtype=torch.uint8, device=dev)
+    with timed("cc_agreement_sums"):
+        _lib.call("cc_agreement_sums", A_nh.data_ptr(), ldA, HA, KA, None if sym else B_nh.data_ptr(), ldB, HB, KB,
+                  n, int(tile_begin), int(tile_end), out.data_ptr() or None, ws.data_ptr() or None, ws.numel(),
+                  stream_ptr())
+    return out
+
+
 def consensus(M: torch.Tensor, I: torch.Tensor) -> torch.Tensor:
     n = M.shape[0]
     C = torch.empty((n, n), dtype=torch.float32, device=M.device)

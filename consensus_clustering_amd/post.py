@@ -226,3 +226,42 @@ def cluster_consensus_from_sums(S, labels, Kc: int) -> np.ndarray:
         T = (int((col >> 32).sum()) << 32) + int((col & 0xFFFFFFFF).sum())
         out[c] = T / ((Nc * (Nc - 1)) << IC_SHIFT)  # int / int: correctly rounded
     return out
+
+
+# ---------------------------------------------------------------- pairwise agreement
+
+AGREEMENT_INDICES = ('ari', 'jaccard')
+
+
+def agreement_from_sums(sums, index: str = 'ari') -> np.ndarray:
+    """Agreement index of every pair of label columns as float64 [...], from the exact int64
+    sums [..., 4] = (s0, s2, r2, c2) of their contingency table N over the shared items
+    (engine.agreement_sums).  They are sklearn's pair_confusion_matrix: tp = C11 = s2 - s0,
+    fp = C01 = c2 - s2, fn = C10 = r2 - s2, tn = C00 = s0^2 - fp - fn - s2, all exact in int64
+    (s0 < 2^31).  NaN where s0 < 2 (no pair of items to judge); 1.0 where fp == fn == 0
+    (sklearn's rule); else
+      'ari':     2 (tp tn - fn fp) / ((tp + fn)(fn + tn) + (tp + fp)(fp + tn))   adjusted_rand_score
+      'jaccard': tp / (tp + fp + fn)                                             Ben-Hur et al. 2002
+    in float64: the integer sums are formed exactly, each converted once, then multiplied."""
+    if index not in AGREEMENT_INDICES:
+        raise ValueError(f"index must be one of {AGREEMENT_INDICES}, got {index!r}")
+    s = np.asarray(sums, dtype=np.int64)
+    if s.ndim < 1 or s.shape[-1] != 4:
+        raise ValueError(f"sums must be [..., 4] = (s0, s2, r2, c2), got shape {s.shape}")
+    s0, s2, r2, c2 = (s[..., j] for j in range(4))
+    tp, fp, fn = s2 - s0, c2 - s2, r2 - s2
+    tn = s0 * s0 - fp - fn - s2
+    out = np.full(s0.shape, np.nan, dtype=np.float64)
+    judged = s0 >= 2
+    same = judged & (fp == 0) & (fn == 0)
+    out[same] = 1.0
+    rest = judged & ~same
+    f = np.float64
+    if index == 'ari':
+        num = 2.0 * (tp.astype(f) * tn.astype(f) - fn.astype(f) * fp.astype(f))
+        den = ((tp + fn).astype(f) * (fn + tn).astype(f) + (tp + fp).astype(f) * (fp + tn).astype(f))
+    else:
+        num = tp.astype(f)
+        den = (tp + fp + fn).astype(f)
+    np.divide(num, den, out=out, where=rest)
+    return out

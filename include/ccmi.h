@@ -20,6 +20,8 @@
  *   cc_coassoc            CC.py:287-290 + :338-344  M += L^T L fused with the 20-bin histogram
  *   cc_consensus          CC.py:372-373  C = f32(M) / f32(I + 1e-6), diag 1
  *   cc_item_consensus     (no reference code) item / cluster consensus sums of C by cluster
+ *   cc_agreement_sums     (no reference code) contingency sums of every pair of label columns:
+ *                         the adjusted Rand / Jaccard agreement of the resamples (int8 MFMA)
  *   cc_kmeans_plan        packing of the (K, init) problems of one resample into units
  *   cc_split_f16          f16 hi/lo operand image of the rows for the k-means MFMAs
  *   cc_kmeans_batched     CC.py:282 clusterer.fit_predict for every (h, K) at once
@@ -167,6 +169,28 @@ int cc_coassoc(const int8_t* labels_nh, int n, int ldl, int Hpad, int K, int64_t
 int cc_item_consensus(const int8_t* labels_nh, int n, int ldl, int Hpad, int K,
                       int64_t tile_begin, int64_t tile_end, const uint16_t* I_tiles,
                       const int32_t* cl, int Kc, int64_t* S, void* stream);
+
+/* Pairwise agreement of label columns (Ben-Hur et al. 2002; the sums behind the adjusted Rand and
+ * Jaccard indices): for every column h1 of group A and h2 of group B, with N[a][b] = #{items i
+ * with A[i][h1] = a and B[i][h2] = b} over the items present in both,
+ *   sums[h1][h2] = { s0 = sum N, s2 = sum N^2, r2 = sum_a (sum_b N)^2, c2 = sum_b (sum_a N)^2 },
+ * exact integers (sklearn's pair_confusion_matrix: C11 = s2 - s0, C01 = c2 - s2, C10 = r2 - s2,
+ * C00 = s0^2 - C01 - C10 - s2).
+ * A_nh: [n][ldA] int8 device, HA columns used, labels in [0, KA); any other byte (0xFF) = absent.
+ * B_nh: [n][ldB] likewise (HB columns, KB), or NULL: A with itself (ldB, HB, KB ignored; sums is
+ *       [HA][HA][4]; only the tiles of the upper triangle run and each stores its mirror too).
+ * Tiles: cc_agreement_num_tiles(HA, HB, KA, KB, symmetric) tiles of 256 x 256 virtual columns; a
+ *       call fills the pairs of [tile_begin, tile_end) with plain stores (the caller zeroes sums;
+ *       disjoint ranges fill disjoint pairs; an empty range launches nothing).
+ * sums: [HA][HB][4] int64 device, 8-B aligned.  workspace: device, 16-B aligned,
+ *       ws_bytes >= cc_agreement_workspace_bytes(n, HA, HB) (HB = 0 for A with itself): the columns
+ *       transposed, written by every call.  KA, KB in [1, 127]; HA, HB, n >= 1.  No atomics on
+ *       global memory and no floating point: the output is bitwise reproducible. */
+size_t cc_agreement_workspace_bytes(int n, int HA, int HB);
+int64_t cc_agreement_num_tiles(int HA, int HB, int KA, int KB, int symmetric);
+int cc_agreement_sums(const int8_t* A_nh, int ldA, int HA, int KA, const int8_t* B_nh, int ldB, int HB,
+                      int KB, int n, int64_t tile_begin, int64_t tile_end, int64_t* sums,
+                      void* workspace, size_t ws_bytes, void* stream);
 
 /* Bin thresholds per co-sampling count i in [0, rows): row i = 21 uint16 T[b] =
  * min{m : bin(f32(m) / f32(i + 1e-6)) >= b} (T[0] = 0, T[20] = 0xFFFF; i + 1 if no m <= i
