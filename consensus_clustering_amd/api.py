@@ -202,6 +202,17 @@ def _hc_validate(X, m, Ks):
                              f"{K} clusters were given for a tree with {m} leaves.")
 
 
+def _int_at_least(v, lo) -> bool:
+    """v is an integer (no bool) >= lo."""
+    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer)) and v >= lo
+
+
+def _finite_non_negative(v) -> bool:
+    """v is a finite real (no bool) >= 0."""
+    return (not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+            and bool(np.isfinite(v) and v >= 0))
+
+
 def _pam_spec(est):
     """scipy's name of the metric of a PAM that the device reproduces (cc_pam_build,
     cc_pam_swap_step, cc_pam_labels), else None: exactly that type (a subclass may override
@@ -212,7 +223,7 @@ def _pam_spec(est):
     metric, max_iter = p.get("metric"), p.get("max_iter")
     if not isinstance(metric, str) or metric not in HC_METRICS:
         return None
-    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 0:
+    if not _int_at_least(max_iter, 0):
         return None
     return HC_METRICS[metric]
 
@@ -240,7 +251,7 @@ def _gmm_spec(est):
     p = est.get_params()
     if not isinstance(p.get("covariance_type"), str) or p["covariance_type"] != 'diag':
         return None
-    return _gmm_params(p)
+    return _em_params(p, ("tol", "reg_covar"))
 
 
 def _gmm_full_spec(est):
@@ -248,24 +259,17 @@ def _gmm_full_spec(est):
     cc_gmm_full_finish): exactly the type FullGMM, under the same rules for its parameters."""
     if type(est) is not FullGMM:
         return None
-    return _gmm_params(est.get_params())
+    return _em_params(est.get_params(), ("tol", "reg_covar"))
 
 
-def _gmm_params(p):
+def _em_params(p, reals):
     """The parameter dict p as the device takes it, else None: integer max_iter >= 1 and
-    n_init >= 1, finite tol >= 0 and reg_covar >= 0."""
-    for name in ("max_iter", "n_init"):
-        v = p.get(name)
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
-            return None
-    for name in ("tol", "reg_covar"):
-        v = p.get(name)
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-            return None
-        if not (np.isfinite(v) and v >= 0):
-            return None
-    return dict(n_init=int(p["n_init"]), max_iter=int(p["max_iter"]), tol=float(p["tol"]),
-                reg_covar=float(p["reg_covar"]))
+    n_init >= 1, and every parameter named in reals finite and >= 0."""
+    if not all(_int_at_least(p.get(name), 1) for name in ("max_iter", "n_init")):
+        return None
+    if not all(_finite_non_negative(p.get(name)) for name in reals):
+        return None
+    return dict(n_init=int(p["n_init"]), max_iter=int(p["max_iter"]), **{name: float(p[name]) for name in reals})
 
 
 def _nmf_spec(est):
@@ -274,17 +278,21 @@ def _nmf_spec(est):
     max_iter >= 1 and n_init >= 1, finite tol >= 0."""
     if type(est) is not NMF:
         return None
-    p = est.get_params()
-    for name in ("max_iter", "n_init"):
-        v = p.get(name)
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
-            return None
-    v = p.get("tol")
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-        return None
-    if not (np.isfinite(v) and v >= 0):
-        return None
-    return dict(n_init=int(p["n_init"]), max_iter=int(p["max_iter"]), tol=float(p["tol"]))
+    return _em_params(est.get_params(), ("tol",))
+
+
+def _to_f64_device(X, dev) -> torch.Tensor:
+    """X (a tensor or an array) as a float64 tensor on the device."""
+    if isinstance(X, torch.Tensor):
+        return X.to(dev, torch.float64)
+    return torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(dev)
+
+
+# what fit() fills for the backend that ran; a refit resets them all first
+_RESULT_ATTRS = ('labels_', '_idx_dev', '_idx_host', 'kmeans_inertia_', 'kmeans_n_iter_', 'kmeans_stats_',
+                 'hc_stats_', 'hc_metric_', 'pam_stats_', 'pam_metric_', 'pam_inertia_', 'pam_n_iter_',
+                 'gmm_stats_', 'gmm_lower_bound_', 'gmm_n_iter_', 'gmm_converged_', 'gmm_covariance_type_',
+                 'nmf_stats_', 'nmf_reconstruction_err_', 'nmf_n_iter_', 'nmf_converged_')
 
 
 class ConsensusClustering:
@@ -422,13 +430,8 @@ class ConsensusClustering:
         rank, W = dist.world()
         # a refit replaces the previous results: their device buffers are dropped first, so the
         # new label matrix and indices reuse that memory instead of growing the pool by a set
-        self.labels_ = self._idx_dev = self._idx_host = None
-        self.kmeans_inertia_ = self.kmeans_n_iter_ = self.kmeans_stats_ = None
-        self.hc_stats_ = self.hc_metric_ = None
-        self.pam_stats_ = self.pam_metric_ = self.pam_inertia_ = self.pam_n_iter_ = None
-        self.gmm_stats_ = self.gmm_lower_bound_ = self.gmm_n_iter_ = self.gmm_converged_ = None
-        self.gmm_covariance_type_ = None
-        self.nmf_stats_ = self.nmf_reconstruction_err_ = self.nmf_n_iter_ = self.nmf_converged_ = None
+        for name in _RESULT_ATTRS:
+            setattr(self, name, None)
         if self.hierarchical not in ('auto', 'device', 'host'):
             raise ValueError("hierarchical must be 'auto', 'device' or 'host'")
         self.partial_ = False
@@ -483,41 +486,19 @@ class ConsensusClustering:
                           "KMeans fits run on the host (sklearn, one fit per resample and K) unless they run on "
                           "the float64 engine (float64 input, or precision='f64')", UserWarning)
             km = None
-        # the estimator as _kmeans_params left it: clusterer_options applied
-        hc = None
-        if Ks and km is None and cols is not None:
-            # each resample's own rows decide (engine.hc_labels finds a row without distances
-            # under the resample's columns), so the whole-X test of _hc_route is not asked
-            hc = _hc_route(_hc_spec(self.clusterer), None, self.hierarchical, degenerate_test=False)
-        elif Ks and km is None:
-            spec = _hc_spec(self.clusterer)
-            if spec is not None and spec[1] in ('cosine', 'correlation') and isinstance(X, torch.Tensor):
-                Xh = X.detach().cpu().numpy()  # the degenerate-row test reads host values
-            else:
-                Xh = X  # read only when a cosine / correlation estimator is routed
-            hc = _hc_route(spec, Xh, self.hierarchical)
-        elif self.hierarchical == 'device':
-            _hc_route(None, None, 'device')
-        pam = None
-        if Ks and km is None and hc is None:
-            pam = _pam_route(_pam_spec(self.clusterer), X if cols is None else None)
-        gmm = None
-        if Ks and km is None and hc is None and pam is None:
-            gmm = _gmm_spec(self.clusterer)
-            self.gmm_covariance_type_ = 'diag' if gmm is not None else None
-            if gmm is None:
-                gmm = _gmm_full_spec(self.clusterer)
-                if gmm is not None and md > engine.GMM_FULL_MD_MAX:
-                    warnings.warn(f"FullGMM runs on the device for at most {engine.GMM_FULL_MD_MAX} features: with "
-                                  f"{md} features the fits run on the host (one fit per resample and K)", UserWarning)
-                    gmm = None
-                self.gmm_covariance_type_ = 'full' if gmm is not None else None
-        nmf = None
-        if Ks and km is None and hc is None and pam is None and gmm is None:
-            nmf = _nmf_spec(self.clusterer)
-        self.backend_ = ('gpu-kmeans' if km is not None else 'gpu-hc' if hc is not None
-                         else 'gpu-pam' if pam is not None else 'gpu-gmm' if gmm is not None
-                         else 'gpu-nmf' if nmf is not None else 'host-clusterer')
+        # the estimator as _kmeans_params left it: clusterer_options applied.  The routes in their
+        # order: the first that gives a spec runs, and none of them is the host loop
+        routes = (('gpu-kmeans', lambda: km), ('gpu-hc', lambda: self._route_hc(X, cols)),
+                  ('gpu-pam', lambda: _pam_route(_pam_spec(self.clusterer), X if cols is None else None)),
+                  ('gpu-gmm', lambda: self._route_gmm(md)), ('gpu-nmf', lambda: _nmf_spec(self.clusterer)))
+        self.backend_, spec = 'host-clusterer', None
+        for name, route in routes if Ks else ():
+            spec = route()
+            if spec is not None:
+                self.backend_ = name
+                break
+        if self.hierarchical == 'device' and self.backend_ != 'gpu-hc':
+            _hc_route(None, None, 'device')  # the trees were not asked (k-means runs, or no K): refused
         precision = self.precision
         if precision == 'auto':
             # the reference's clusterer computes in X's dtype (CC.py:282): float64 input keeps
@@ -527,15 +508,14 @@ class ConsensusClustering:
         if precision not in ('f64', 'fast'):
             raise ValueError("precision must be 'auto', 'f64' or 'fast'")
         self.precision_ = precision if km is not None else None
-        if Ks and km is not None:
+        if km is not None:
             bk = BatchedKMeans(Ks, n_init=km["n_init"], max_iter=km["max_iter"], tol=km["tol"],
                                random_state=self.random_state,
                                workspace_budget=self.workspace_budget)
             self.kmeans_n_iter_ = torch.zeros((len(Ks), H), dtype=torch.int32, device=dev)
             if precision == 'f64':
                 # float64 input: the reference's clusterer runs in float64 (CC.py:282)
-                X64 = (X.to(dev, torch.float64) if isinstance(X, torch.Tensor)
-                       else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(dev))
+                X64 = _to_f64_device(X, dev)
                 self.kmeans_inertia_ = torch.zeros((len(Ks), H), dtype=torch.float64, device=dev)
                 # feature subsampling: every rank holds all H column rows and runs its [h0, h1)
                 bk.run_f64(X64.contiguous(), idx_d, n, H, m, h0, h1, labels,
@@ -550,22 +530,19 @@ class ConsensusClustering:
                        inertia=self.kmeans_inertia_, n_iter=self.kmeans_n_iter_, Xhl=Xhl,
                        scale_exp=sexp)
             self.kmeans_stats_ = bk.stats
-        elif Ks and hc is not None:
-            self.hc_metric_ = hc[1]
-            self.hc_stats_ = self._fit_hierarchical(X, wdtype, hc[0], hc[1], idx_d, n, m, h0, h1, Ks, labels, dev,
+        elif self.backend_ == 'gpu-hc':
+            self.hc_metric_ = spec[1]
+            self.hc_stats_ = self._fit_hierarchical(X, wdtype, spec[0], spec[1], idx_d, n, m, h0, h1, Ks, labels, dev,
                                                     cols=cols)
-        elif Ks and pam is not None:
-            self.pam_metric_ = pam
+        elif self.backend_ == 'gpu-pam':
+            self.pam_metric_ = spec
             self.pam_inertia_ = torch.zeros((len(Ks), H), dtype=torch.float64, device=dev)
             self.pam_n_iter_ = torch.zeros((len(Ks), H), dtype=torch.int32, device=dev)
-            self.pam_stats_ = self._fit_pam(X, wdtype, pam, idx_d, n, m, h0, h1, Ks, labels, dev, cols=cols)
-        elif Ks and gmm is not None:
-            self.gmm_lower_bound_ = torch.zeros((len(Ks), H), dtype=torch.float64, device=dev)
-            self.gmm_n_iter_ = torch.zeros((len(Ks), H), dtype=torch.int32, device=dev)
-            self.gmm_converged_ = torch.zeros((len(Ks), H), dtype=torch.uint8, device=dev)
-            self.gmm_stats_ = self._fit_gmm(X, wdtype, gmm, idx_d, n, m, h0, h1, Ks, labels, dev, cols=cols)
-        elif Ks and nmf is not None:
-            self.nmf_stats_ = self._fit_nmf(X, wdtype, nmf, idx_d, n, m, h0, h1, Ks, labels, dev, cols=cols)
+            self.pam_stats_ = self._fit_pam(X, wdtype, spec, idx_d, n, m, h0, h1, Ks, labels, dev, cols=cols)
+        elif self.backend_ == 'gpu-gmm':
+            self.gmm_stats_ = self._fit_gmm(X, wdtype, spec, idx_d, n, m, h0, h1, Ks, labels, dev, cols=cols)
+        elif self.backend_ == 'gpu-nmf':
+            self.nmf_stats_ = self._fit_nmf(X, wdtype, spec, idx_d, n, m, h0, h1, Ks, labels, dev, cols=cols)
         elif Ks:
             if isinstance(X, torch.Tensor):
                 X = X.cpu().numpy()
@@ -674,74 +651,107 @@ class ConsensusClustering:
                                                                 max_iter=max_iter, X=Xd, cols_d=cols_d, metric=metric,
                                                                 inertia=self.pam_inertia_, n_iter=self.pam_n_iter_))
 
+    def _route_hc(self, X, cols):
+        """_hc_route for the estimator.  Under feature subsampling each resample's own rows decide
+        (engine.hc_labels finds a row without distances under the resample's columns), so the
+        whole-X test is not asked; else it reads host values, for a cosine / correlation estimator
+        alone."""
+        spec = _hc_spec(self.clusterer)
+        if cols is not None:
+            return _hc_route(spec, None, self.hierarchical, degenerate_test=False)
+        if spec is not None and spec[1] in ('cosine', 'correlation') and isinstance(X, torch.Tensor):
+            X = X.detach().cpu().numpy()
+        return _hc_route(spec, X, self.hierarchical)
+
+    def _route_gmm(self, md):
+        """The parameters of the GMM or FullGMM that the device runs, or None; gmm_covariance_type_
+        tells which.  A FullGMM over more than GMM_FULL_MD_MAX features runs in the host loop."""
+        spec, self.gmm_covariance_type_ = _gmm_spec(self.clusterer), 'diag'
+        if spec is None:
+            spec, self.gmm_covariance_type_ = _gmm_full_spec(self.clusterer), 'full'
+            if spec is not None and md > engine.GMM_FULL_MD_MAX:
+                warnings.warn(f"FullGMM runs on the device for at most {engine.GMM_FULL_MD_MAX} features: with "
+                              f"{md} features the fits run on the host (one fit per resample and K)", UserWarning)
+                spec = None
+        if spec is None:
+            self.gmm_covariance_type_ = None
+        return spec
+
     def _fit_gmm(self, X, wdtype, spec, idx_d, n, m, h0, h1, Ks, labels, dev, cols=None):
         """CC.py:282 for GMM(**spec), or FullGMM(**spec) where gmm_covariance_type_ is 'full', on the
-        device: the refusals from host values, the plan when a
-        workspace_budget is set (too small: raises before any launch), X as float64 on the device
-        (a float32 X is cast, with a warning: GMM computes in float64) and the column list, then
-        EM of every (resample, K) of [h0, h1) into this rank's columns of the label matrix, of
-        gmm_lower_bound_, gmm_n_iter_ and gmm_converged_ (engine.gmm_labels).  A problem with a
-        variance (a Cholesky pivot under 'full') that is not positive raises sklearn's ValueError on every rank
-        (dist.first_failure)."""
+        device (_fit_on_rows): EM of every (resample, K) of [h0, h1) into this rank's columns of the
+        label matrix, of gmm_lower_bound_, gmm_n_iter_ and gmm_converged_ (engine.gmm_labels).  A
+        problem with a variance (a Cholesky pivot under 'full') that is not positive raises
+        sklearn's ValueError on every rank."""
         covariance = self.gmm_covariance_type_
         who = "FullGMM" if covariance == 'full' else "GMM"
-        if isinstance(X, torch.Tensor):
-            _gmm_validate(None if bool(torch.isfinite(X).all()) else X.detach().cpu().numpy(), m, Ks, who)
-        else:
+
+        def validate(X):
+            if isinstance(X, torch.Tensor):
+                X = None if bool(torch.isfinite(X).all()) else X.detach().cpu().numpy()
             _gmm_validate(X, m, Ks, who)
-        md = X.shape[1] if cols is None else cols.shape[1]
-        if self.workspace_budget is not None:
-            engine.gmm_plan(n, m, max(h1 - h0, 1), Ks, md, self.workspace_budget, covariance)
-        if np.dtype(wdtype) != np.float64:
-            warnings.warn("GMM computes in float64: the float32 X is cast to float64 (sklearn's GaussianMixture "
-                          "would compute in float32)", UserWarning)
-        X64 = (X.to(dev, torch.float64) if isinstance(X, torch.Tensor)
-               else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(dev)).contiguous()
-        cols_d = None if cols is None else torch.from_numpy(cols).to(dev)
-        stats = code = None
-        try:
-            stats = engine.gmm_labels(X64, idx_d, h0, h1, Ks, labels, budget=self.workspace_budget,
-                                      seed=int(self.random_state), cols_d=cols_d,
-                                      lower_bound=self.gmm_lower_bound_, n_iter=self.gmm_n_iter_,
-                                      converged=self.gmm_converged_, covariance=covariance, **spec)
-        except engine.IllDefinedMixture:
-            code = 1
-        if dist.first_failure(code, dev) is not None:
-            raise engine.IllDefinedMixture()
-        return stats
+
+        return self._fit_on_rows(
+            X, wdtype, dev, cols, idx_d.shape[0], len(Ks), validate,
+            lambda budget, md: engine.gmm_plan(n, m, max(h1 - h0, 1), Ks, md, budget, covariance),
+            ("GMM", "GaussianMixture"), ('gmm_lower_bound_', 'gmm_n_iter_', 'gmm_converged_'),
+            lambda X64, cols_d, value, n_iter, converged: engine.gmm_labels(
+                X64, idx_d, h0, h1, Ks, labels, budget=self.workspace_budget, seed=int(self.random_state),
+                cols_d=cols_d, lower_bound=value, n_iter=n_iter, converged=converged, covariance=covariance, **spec),
+            engine.IllDefinedMixture)
 
     def _fit_nmf(self, X, wdtype, spec, idx_d, n, m, h0, h1, Ks, labels, dev, cols=None):
-        """CC.py:282 for NMF(**spec) on the device: the refusals from host values on every rank
-        before any launch (X that is not finite or holds a negative entry; a device tensor is
-        tested with torch), the plan when a workspace_budget is set (too small: raises before any
-        launch), X as float64 on the device (a float32 X is cast, with a warning: NMF computes in
-        float64) and the column list, then the multiplicative updates of every (resample, K) of
-        [h0, h1) into this rank's columns of the label matrix, of nmf_reconstruction_err_,
-        nmf_n_iter_ and nmf_converged_ (engine.nmf_labels).  No problem can fail."""
-        if isinstance(X, torch.Tensor):
+        """CC.py:282 for NMF(**spec) on the device (_fit_on_rows; X that is not finite or holds a
+        negative entry is refused, a device tensor is tested with torch): the multiplicative
+        updates of every (resample, K) of [h0, h1) into this rank's columns of the label matrix,
+        of nmf_reconstruction_err_, nmf_n_iter_ and nmf_converged_ (engine.nmf_labels).  No
+        problem can fail."""
+        def validate(X):
+            if not isinstance(X, torch.Tensor):
+                return _nmf_validate(X)
             if not bool(torch.isfinite(X).all()):
                 refuse_not_finite(X.detach().cpu().numpy())
             if X.numel() and bool((X < 0).any()):
                 raise ValueError(_NMF_NEGATIVE)
-        else:
-            _nmf_validate(X)
-        md = X.shape[1] if cols is None else cols.shape[1]
+
+        return self._fit_on_rows(
+            X, wdtype, dev, cols, idx_d.shape[0], len(Ks), validate,
+            lambda budget, md: engine.nmf_plan(n, m, max(h1 - h0, 1), Ks, md, budget, spec["n_init"]),
+            ("NMF", "NMF"), ('nmf_reconstruction_err_', 'nmf_n_iter_', 'nmf_converged_'),
+            lambda X64, cols_d, value, n_iter, converged: engine.nmf_labels(
+                X64, idx_d, h0, h1, Ks, labels, budget=self.workspace_budget, seed=int(self.random_state),
+                cols_d=cols_d, reconstruction_err=value, n_iter=n_iter, converged=converged, **spec))
+
+    def _fit_on_rows(self, X, wdtype, dev, cols, H, nK, validate, plan, names, outputs, run, failure=None):
+        """What the device clusterers over the rows of X share (GMM, FullGMM, NMF): the refusals of
+        validate(X) from host values on every rank before any launch, plan(budget, md) when a
+        workspace_budget is set (too small: raises before any launch), the warning that a float32
+        X is cast (names: ours and sklearn's of the model, which computes in float64 here), the
+        [nK, H] outputs (float64 value, int32 n_iter, uint8 converged) under the attribute names
+        `outputs`, X as float64 on the device, the column list, and run(X64, cols_d, value, n_iter,
+        converged) -> stats.  failure: the exception of run that the ranks agree on
+        (dist.first_failure), so that all raise it."""
+        validate(X)
         if self.workspace_budget is not None:
-            engine.nmf_plan(n, m, max(h1 - h0, 1), Ks, md, self.workspace_budget, spec["n_init"])
+            plan(self.workspace_budget, X.shape[1] if cols is None else cols.shape[1])
         if np.dtype(wdtype) != np.float64:
-            warnings.warn("NMF computes in float64: the float32 X is cast to float64 (sklearn's NMF would compute "
-                          "in float32)", UserWarning)
-        H = idx_d.shape[0]
-        self.nmf_reconstruction_err_ = torch.zeros((len(Ks), H), dtype=torch.float64, device=dev)
-        self.nmf_n_iter_ = torch.zeros((len(Ks), H), dtype=torch.int32, device=dev)
-        self.nmf_converged_ = torch.zeros((len(Ks), H), dtype=torch.uint8, device=dev)
-        X64 = (X.to(dev, torch.float64) if isinstance(X, torch.Tensor)
-               else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(dev)).contiguous()
+            warnings.warn(f"{names[0]} computes in float64: the float32 X is cast to float64 (sklearn's {names[1]} "
+                          "would compute in float32)", UserWarning)
+        outs = [torch.zeros((nK, H), dtype=dt, device=dev) for dt in (torch.float64, torch.int32, torch.uint8)]
+        for name, t in zip(outputs, outs):
+            setattr(self, name, t)
+        X64 = _to_f64_device(X, dev).contiguous()
         cols_d = None if cols is None else torch.from_numpy(cols).to(dev)
-        return engine.nmf_labels(X64, idx_d, h0, h1, Ks, labels, budget=self.workspace_budget,
-                                 seed=int(self.random_state), cols_d=cols_d,
-                                 reconstruction_err=self.nmf_reconstruction_err_, n_iter=self.nmf_n_iter_,
-                                 converged=self.nmf_converged_, **spec)
+        if failure is None:
+            return run(X64, cols_d, *outs)
+        stats = code = None
+        try:
+            stats = run(X64, cols_d, *outs)
+        except failure:
+            code = 1
+        if dist.first_failure(code, dev) is not None:
+            raise failure()
+        return stats
 
     def _fit_on_distances(self, X, wdtype, metric, n, m, Ks, dev, cols, validate, plan, run):
         """What the device clusterers over pdist(X, metric) share (the trees and PAM): the

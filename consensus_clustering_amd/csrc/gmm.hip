@@ -22,11 +22,13 @@
 //   logsumexp, lower bound   gmm_shared.hpp: the row tail of the E-step, gmm_decide and gmm_pick,
 //                 which the full-covariance kernels (gmm_full.hip) share with this file
 //   per component constants   j = 0 .. md - 1 in order; the weight sum c = 0 .. K - 1 in order
+//
+// cc_gmm_gather and cc_gmm_active, defined here, serve every row-batch clusterer (gmm_full.hip,
+// nmf.hip): the gather knows nothing about mixtures, and cc_gmm_active reads only the two header
+// words that all three workspaces share (batch_shared.hpp).
 #include "gmm_shared.hpp"
 
 namespace {
-
-constexpr int ESTEP_CHUNKS = 128;  // most workgroups along the rows of one problem
 
 // the arrays of one problem, in this order: resp [m][Kp], sums [Kp][2 md + 1], W [Kp][2 md],
 // cst / ldet / logw [Kp] each, part [ceil(m / 16)]
@@ -97,14 +99,14 @@ __global__ __launch_bounds__(GT) void gmm_estep(Args a, const int* __restrict__ 
         const int j = 4 * s + q;
         const double av = wp[j];
         const double x = rin ? xr[j < md ? j : j - md] : 0.0;
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, j < md ? x : x * x, acc, 0, 0, 0);
+        acc = mfma(av, j < md ? x : x * x, acc);
       }
       if (ld & 3) {  // the last, partial step of 4
         const int j = 4 * S + q;
         const bool in = j < ld;
         const double av = in ? wp[j] : 0.0;
         const double x = in && rin ? xr[j < md ? j : j - md] : 0.0;
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, j < md ? x : x * x, acc, 0, 0, 0);
+        acc = mfma(av, j < md ? x : x * x, acc);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(GT) void gmm_mstep(Args a, int init, double reg_cov
       const double av = rp[r * Kp];
       const double x = xp[r * md];
       const double bv = kind == 0 ? x : kind == 1 ? x * x : kind == 2 ? 1.0 : 0.0;
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+      acc = mfma(av, bv, acc);
     }
     if (m & 3) {  // the last, partial step of 4
       const size_t r = 4 * S + q;
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(GT) void gmm_mstep(Args a, int init, double reg_cov
       const double av = in ? rp[r * Kp] : 0.0;
       const double x = in ? xp[r * md] : 0.0;
       const double bv = !in ? 0.0 : kind == 0 ? x : kind == 1 ? x * x : kind == 2 ? 1.0 : 0.0;
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+      acc = mfma(av, bv, acc);
     }
     if (j < nc) {
 #pragma unroll
@@ -211,24 +213,19 @@ __global__ __launch_bounds__(GT) void gmm_mstep(Args a, int init, double reg_cov
   if (tid == 0 && bad_s) gmm_mark_failed(a.word, a.st[p]);
 }
 
-bool shape_ok(int m, int md, int B, const int* Ks, int nK) {
-  return md >= 1 && md <= (1 << 20) && batch_ok(m, B, Ks, nK);
-}
+constexpr int MD_MAX = 1 << 20;
 
-size_t layout(int m, int md, int B, const int* Ks, int nK, void* ws, Args* a) {
-  return layout(prob_doubles, m, md, B, Ks, nK, ws, a);
-}
-
-dim3 estep_grid(int m, int B, int nK) {
-  const int ntile = (m + 15) / 16, chunks = (ntile + GW - 1) / GW;
-  return dim3(chunks < ESTEP_CHUNKS ? chunks : ESTEP_CHUNKS, B * nK);
+// batch_enter for this file's problems
+bool enter(Args* a, bool ok, const double* Xb, int m, int md, int B, const int* Ks, int nK, void* ws, size_t ws_bytes,
+           const char* error) {
+  return batch_enter(a, prob_doubles, MD_MAX, true, ok, Xb, m, md, B, Ks, nK, ws, ws_bytes, error);
 }
 
 }  // namespace
 
 extern "C" size_t cc_gmm_workspace_bytes(int m, int md, int B, const int* Ks, int nK) {
-  if (!shape_ok(m, md, B, Ks, nK)) return 0;
-  return layout(m, md, B, Ks, nK, nullptr, nullptr);
+  if (!batch_ok(m, md, B, Ks, nK, MD_MAX, true)) return 0;
+  return layout<State>(prob_doubles, m, md, B, Ks, nK, nullptr, nullptr);
 }
 
 extern "C" int cc_gmm_gather(const double* X, int64_t n, int d, const int* idx, const int* cols, int B, int m, int md,
@@ -247,15 +244,11 @@ extern "C" int cc_gmm_gather(const double* X, int64_t n, int d, const int* idx, 
 extern "C" int cc_gmm_start(const double* Xb, const int* idx, int B, int m, int md, const int* Ks, int nK,
                             const uint8_t* init_labels, int64_t n, int64_t ldl, int col_begin, double reg_covar,
                             void* workspace, size_t ws_bytes, void* stream) {
-  if (!Xb || !idx || !init_labels || !workspace || !shape_ok(m, md, B, Ks, nK) || n < m || col_begin < 0 ||
-      ldl < static_cast<int64_t>(col_begin) + B || !(reg_covar >= 0.0) ||
-      ws_bytes < cc_gmm_workspace_bytes(m, md, B, Ks, nK)) {
-    cc::set_error("cc_gmm_start: bad arguments (1 <= K <= min(m, 127), at most 127 values of K, B * nK <= 65535)");
-    return CC_ERR_ARG;
-  }
   Args a;
-  layout(m, md, B, Ks, nK, workspace, &a);
-  a.Xb = Xb;
+  if (!enter(&a, idx && init_labels && n >= m && columns_ok(col_begin, B, ldl) && reg_covar >= 0.0, Xb, m, md, B, Ks,
+             nK, workspace, ws_bytes,
+             "cc_gmm_start: bad arguments (1 <= K <= min(m, 127), at most 127 values of K, B * nK <= 65535)"))
+    return CC_ERR_ARG;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(workspace, 0, HEADER, st) != hipSuccess) return launch_error("cc_gmm_start");
   const int chunks = (m + GT - 1) / GT;
@@ -267,19 +260,15 @@ extern "C" int cc_gmm_start(const double* Xb, const int* idx, int B, int m, int 
 
 extern "C" int cc_gmm_em_step(const double* Xb, int B, int m, int md, const int* Ks, int nK, double tol,
                               double reg_covar, int max_iter, void* workspace, size_t ws_bytes, void* stream) {
-  if (!Xb || !workspace || !shape_ok(m, md, B, Ks, nK) || !(tol >= 0.0) || !(reg_covar >= 0.0) || max_iter < 1 ||
-      ws_bytes < cc_gmm_workspace_bytes(m, md, B, Ks, nK)) {
-    cc::set_error("cc_gmm_em_step: bad arguments");
-    return CC_ERR_ARG;
-  }
   Args a;
-  layout(m, md, B, Ks, nK, workspace, &a);
-  a.Xb = Xb;
+  if (!enter(&a, tol >= 0.0 && reg_covar >= 0.0 && max_iter >= 1, Xb, m, md, B, Ks, nK, workspace, ws_bytes,
+             "cc_gmm_em_step: bad arguments"))
+    return CC_ERR_ARG;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(a.word, 0, sizeof(int), st) != hipSuccess) return launch_error("cc_gmm_em_step");
-  const size_t lds = static_cast<size_t>(GW) * max_kp(Ks, nK) * 16 * sizeof(double);
-  hipLaunchKernelGGL(gmm_estep<0>, estep_grid(m, B, nK), dim3(GT), lds, st, a, static_cast<const int*>(nullptr),
-                     static_cast<uint8_t*>(nullptr), static_cast<int64_t>(0), static_cast<int64_t>(0), 0);
+  hipLaunchKernelGGL(gmm_estep<0>, row_grid(m, B, nK), dim3(GT), tile_lds(Ks, nK), st, a,
+                     static_cast<const int*>(nullptr), static_cast<uint8_t*>(nullptr), static_cast<int64_t>(0),
+                     static_cast<int64_t>(0), 0);
   hipLaunchKernelGGL(gmm_decide<Args>, dim3((B * nK + GW - 1) / GW), dim3(GT), 0, st, a, tol, max_iter);
   hipLaunchKernelGGL(gmm_mstep, dim3(B * nK), dim3(GT), 0, st, a, 0, reg_covar);
   return launch_error("cc_gmm_em_step");
@@ -306,20 +295,15 @@ extern "C" int cc_gmm_finish(const double* Xb, const int* idx, int B, int m, int
                              int keep_best, int h_begin, uint8_t* labels, int64_t n, int64_t ldl, double* lower_bound,
                              int* n_iter, uint8_t* converged, int64_t ldo, void* workspace, size_t ws_bytes,
                              void* stream) {
-  if (!Xb || !idx || !labels || !workspace || !shape_ok(m, md, B, Ks, nK) || h_begin < 0 || n < m ||
-      ldl < static_cast<int64_t>(h_begin) + B ||
-      ((lower_bound || n_iter || converged) && ldo < static_cast<int64_t>(h_begin) + B) ||
-      ws_bytes < cc_gmm_workspace_bytes(m, md, B, Ks, nK)) {
-    cc::set_error("cc_gmm_finish: bad arguments");
-    return CC_ERR_ARG;
-  }
   Args a;
-  layout(m, md, B, Ks, nK, workspace, &a);
-  a.Xb = Xb;
+  if (!enter(&a, idx && labels && n >= m && columns_ok(h_begin, B, ldl) &&
+                 (!(lower_bound || n_iter || converged) || columns_ok(h_begin, B, ldo)),
+             Xb, m, md, B, Ks, nK, workspace, ws_bytes, "cc_gmm_finish: bad arguments"))
+    return CC_ERR_ARG;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(gmm_pick<Args>, dim3((B * nK + GT - 1) / GT), dim3(GT), 0, st, a, keep_best, h_begin, lower_bound,
                      n_iter, converged, ldo);
-  const size_t lds = static_cast<size_t>(GW) * max_kp(Ks, nK) * 16 * sizeof(double);
-  hipLaunchKernelGGL(gmm_estep<1>, estep_grid(m, B, nK), dim3(GT), lds, st, a, idx, labels, n, ldl, h_begin);
+  hipLaunchKernelGGL(gmm_estep<1>, row_grid(m, B, nK), dim3(GT), tile_lds(Ks, nK), st, a, idx, labels, n, ldl,
+                     h_begin);
   return launch_error("cc_gmm_finish");
 }

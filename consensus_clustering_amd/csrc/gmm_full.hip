@@ -1,8 +1,9 @@
 // K13: batched EM for the full-covariance Gaussian mixture base clusterer (gmm.py FullGMM,
 // DESIGN.md K13).
 //
-// The batch, the rows Xb [B][m][md] (cc_gmm_gather), the workspace header and the per-problem
-// State are gmm.hip's (gmm_shared.hpp), so cc_gmm_active reads this workspace too.  One EM
+// The batch, the rows Xb [B][m][md] (cc_gmm_gather) and the workspace header are the batch frame's
+// (batch_shared.hpp), so cc_gmm_active reads this workspace too; the per-problem State is
+// gmm.hip's (gmm_shared.hpp).  One EM
 // iteration of every active problem is five launches, ordered by the stream:
 //   gmmf_estep   (row chunks x problems) a workgroup owns 4 * tpw 16-row tiles.  Per component c it
 //                stages the precision factor P_c (upper triangular, [md][md]) and mu_c P_c in LDS
@@ -40,7 +41,7 @@
 //   substitution  z_i = (e_i - sum_k l_ik z_k) / l_ii, the terms leave in the order k = b .. i - 1
 //   mu P, log det, weight sum   i = 0 .. j in order; j = 0 .. md - 1 in order; c = 0 .. K - 1 in order
 //
-// Limits (shape_ok): 1 <= K <= min(m, 127), 1 <= md <= 128, and gmm.hip's on m, B and the problem
+// Limits (batch_ok): 1 <= K <= min(m, 127), 1 <= md <= 128, and gmm.hip's on m, B and the problem
 // count.  The largest LDS stages: the E-step's 72 KiB block triangle of P_c at md = 128 next to
 // 4 * tpw * Kp * 128 bytes of log probabilities (at most 137 KiB), the factor's 131 KiB at md = 128;
 // gfx950 lets a workgroup declare 160 KiB once the kernel's dynamic limit is raised.
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(GT) void gmmf_estep(Args a, int tpw, const int* __r
         for (int jt = 0; jt < NJT; ++jt) {
           if (jt >= j0 && jt < njt) {
             const double av = in ? Ps[tri_off(jt) + i * 16 + lr] : 0.0;
-            acc[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, x, acc[jt], 0, 0, 0);
+            acc[jt] = mfma(av, x, acc[jt]);
           }
         }
       }
@@ -201,14 +202,14 @@ __global__ __launch_bounds__(GT) void gmmf_means(Args a, int init) {
       const size_t r = 4 * s + q;
       const double av = rp[r * Kp];
       const double x = xp[r * md];
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, kind == 0 ? x : kind == 2 ? 1.0 : 0.0, acc, 0, 0, 0);
+      acc = mfma(av, kind == 0 ? x : kind == 2 ? 1.0 : 0.0, acc);
     }
     if (m & 3) {  // the last, partial step of 4
       const size_t r = 4 * S + q;
       const bool in = r < static_cast<size_t>(m);
       const double av = in ? rp[r * Kp] : 0.0;
       const double x = in ? xp[r * md] : 0.0;
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, !in ? 0.0 : kind == 0 ? x : kind == 2 ? 1.0 : 0.0, acc, 0, 0, 0);
+      acc = mfma(av, !in ? 0.0 : kind == 0 ? x : kind == 2 ? 1.0 : 0.0, acc);
     }
     if (j < nc) {
 #pragma unroll
@@ -262,7 +263,7 @@ __global__ __launch_bounds__(GT) void gmmf_cov(Args a, int init, double reg_cova
     const double w = rp[r * Kp];
     const double av = iin ? w * (xi[r * md] - mui) : 0.0;
     const double bv = jin ? xj[r * md] - muj : 0.0;
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+    acc = mfma(av, bv, acc);
   }
   if (m & 3) {  // the last, partial step of 4
     const size_t r = 4 * S + q;
@@ -270,7 +271,7 @@ __global__ __launch_bounds__(GT) void gmmf_cov(Args a, int init, double reg_cova
     const double w = in ? rp[r * Kp] : 0.0;
     const double av = in && iin ? w * (xi[r * md] - mui) : 0.0;
     const double bv = in && jin ? xj[r * md] - muj : 0.0;
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+    acc = mfma(av, bv, acc);
   }
   const double nk = pr.nk[c];
   double* C = pr.P + static_cast<size_t>(c) * md * md;
@@ -353,12 +354,10 @@ __global__ __launch_bounds__(GT) void gmmf_factor(Args a, int init) {
   }
 }
 
-bool shape_ok(int m, int md, int B, const int* Ks, int nK) {
-  return md >= 1 && md <= GMMF_MDMAX && batch_ok(m, B, Ks, nK);
-}
-
-size_t layout(int m, int md, int B, const int* Ks, int nK, void* ws, Args* a) {
-  return layout(prob_doubles, m, md, B, Ks, nK, ws, a);
+// batch_enter for this file's problems
+bool enter(Args* a, bool ok, const double* Xb, int m, int md, int B, const int* Ks, int nK, void* ws, size_t ws_bytes,
+           const char* error) {
+  return batch_enter(a, prob_doubles, GMMF_MDMAX, true, ok, Xb, m, md, B, Ks, nK, ws, ws_bytes, error);
 }
 
 int max_k(const int* Ks, int nK) {
@@ -432,23 +431,19 @@ int launch_mstep(const Args& a, const int* Ks, int nK, int init, double reg_cova
 }  // namespace
 
 extern "C" size_t cc_gmm_full_workspace_bytes(int m, int md, int B, const int* Ks, int nK) {
-  if (!shape_ok(m, md, B, Ks, nK)) return 0;
-  return layout(m, md, B, Ks, nK, nullptr, nullptr);
+  if (!batch_ok(m, md, B, Ks, nK, GMMF_MDMAX, true)) return 0;
+  return layout<State>(prob_doubles, m, md, B, Ks, nK, nullptr, nullptr);
 }
 
 extern "C" int cc_gmm_full_start(const double* Xb, const int* idx, int B, int m, int md, const int* Ks, int nK,
                                  const uint8_t* init_labels, int64_t n, int64_t ldl, int col_begin, double reg_covar,
                                  void* workspace, size_t ws_bytes, void* stream) {
-  if (!Xb || !idx || !init_labels || !workspace || !shape_ok(m, md, B, Ks, nK) || n < m || col_begin < 0 ||
-      ldl < static_cast<int64_t>(col_begin) + B || !(reg_covar >= 0.0) ||
-      ws_bytes < cc_gmm_full_workspace_bytes(m, md, B, Ks, nK)) {
-    cc::set_error("cc_gmm_full_start: bad arguments (1 <= K <= min(m, 127), md <= 128, at most 127 values of K, "
-                  "B * nK <= 65535)");
-    return CC_ERR_ARG;
-  }
   Args a;
-  layout(m, md, B, Ks, nK, workspace, &a);
-  a.Xb = Xb;
+  if (!enter(&a, idx && init_labels && n >= m && columns_ok(col_begin, B, ldl) && reg_covar >= 0.0, Xb, m, md, B, Ks,
+             nK, workspace, ws_bytes,
+             "cc_gmm_full_start: bad arguments (1 <= K <= min(m, 127), md <= 128, at most 127 values of K, "
+             "B * nK <= 65535)"))
+    return CC_ERR_ARG;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(workspace, 0, HEADER, st) != hipSuccess) return launch_error("cc_gmm_full_start");
   const int chunks = (m + GT - 1) / GT;
@@ -460,14 +455,10 @@ extern "C" int cc_gmm_full_start(const double* Xb, const int* idx, int B, int m,
 
 extern "C" int cc_gmm_full_em_step(const double* Xb, int B, int m, int md, const int* Ks, int nK, double tol,
                                    double reg_covar, int max_iter, void* workspace, size_t ws_bytes, void* stream) {
-  if (!Xb || !workspace || !shape_ok(m, md, B, Ks, nK) || !(tol >= 0.0) || !(reg_covar >= 0.0) || max_iter < 1 ||
-      ws_bytes < cc_gmm_full_workspace_bytes(m, md, B, Ks, nK)) {
-    cc::set_error("cc_gmm_full_em_step: bad arguments");
-    return CC_ERR_ARG;
-  }
   Args a;
-  layout(m, md, B, Ks, nK, workspace, &a);
-  a.Xb = Xb;
+  if (!enter(&a, tol >= 0.0 && reg_covar >= 0.0 && max_iter >= 1, Xb, m, md, B, Ks, nK, workspace, ws_bytes,
+             "cc_gmm_full_em_step: bad arguments"))
+    return CC_ERR_ARG;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(a.word, 0, sizeof(int), st) != hipSuccess) return launch_error("cc_gmm_full_em_step");
   int rc = launch_estep<0>(a, Ks, nK, st, nullptr, nullptr, 0, 0, 0, "cc_gmm_full_em_step");
@@ -481,16 +472,11 @@ extern "C" int cc_gmm_full_finish(const double* Xb, const int* idx, int B, int m
                                   int keep_best, int h_begin, uint8_t* labels, int64_t n, int64_t ldl,
                                   double* lower_bound, int* n_iter, uint8_t* converged, int64_t ldo, void* workspace,
                                   size_t ws_bytes, void* stream) {
-  if (!Xb || !idx || !labels || !workspace || !shape_ok(m, md, B, Ks, nK) || h_begin < 0 || n < m ||
-      ldl < static_cast<int64_t>(h_begin) + B ||
-      ((lower_bound || n_iter || converged) && ldo < static_cast<int64_t>(h_begin) + B) ||
-      ws_bytes < cc_gmm_full_workspace_bytes(m, md, B, Ks, nK)) {
-    cc::set_error("cc_gmm_full_finish: bad arguments");
-    return CC_ERR_ARG;
-  }
   Args a;
-  layout(m, md, B, Ks, nK, workspace, &a);
-  a.Xb = Xb;
+  if (!enter(&a, idx && labels && n >= m && columns_ok(h_begin, B, ldl) &&
+                 (!(lower_bound || n_iter || converged) || columns_ok(h_begin, B, ldo)),
+             Xb, m, md, B, Ks, nK, workspace, ws_bytes, "cc_gmm_full_finish: bad arguments"))
+    return CC_ERR_ARG;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(gmm_pick<Args>, dim3((B * nK + GT - 1) / GT), dim3(GT), 0, st, a, keep_best, h_begin, lower_bound,
                      n_iter, converged, ldo);

@@ -1,7 +1,7 @@
 // What the diagonal (gmm.hip, K12) and the full-covariance (gmm_full.hip, K13) mixture kernels
-// share: the workspace header and the per-problem State (so cc_gmm_active reads either
-// workspace), the batch arguments, the one-hot start, the row tail of the E-step from the weighted
-// log probabilities of a 16-row tile onward, and the decide and pick kernels.
+// share on top of the batch frame (batch_shared.hpp): the per-problem State, the one-hot start, the
+// row tail of the E-step from the weighted log probabilities of a 16-row tile onward, and the
+// decide and pick kernels.
 //
 // A translation unit that includes this file defines, in its own unnamed namespace,
 //   struct Prob { double *resp, *part; int K, Kp; ... };   // the arrays of one problem
@@ -12,48 +12,19 @@
 // no floating-point atomic anywhere):
 //   logsumexp     per row, lane q = 0..3 adds its components q, q + 4, .. in order, then (q0 + q1) +
 //                 (q2 + q3)
-//   lower bound   per 16-row tile rows 0..15 in order; per problem lane l adds tiles l, l + 64, .. in
-//                 order, then a butterfly over the 64 lanes
+//   lower bound   per 16-row tile rows 0..15 in order; per problem sum_parts (batch_shared.hpp)
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-#include <string>
-
-#include "ccmi_internal.h"
-
-#pragma clang fp contract(off)
+#include "batch_shared.hpp"
 
 namespace {
-
-constexpr int GT = 256;  // threads of a workgroup
-constexpr int GW = GT / 64;
-constexpr int GMM_KMAX = 127;
-constexpr int GMM_NKMAX = 127;
-constexpr size_t HEADER = 256;  // word[0]: problems still active, word[1]: problems that failed
-
-using f64x4 = __attribute__((ext_vector_type(4))) double;
 
 struct State {
   double prev, lower, best;  // the bound before and after the last E-step; the best init's so far
   int n_iter, active, converged, failed, win, mrun;
 };
 
-struct Args {
-  int m, md, B, nK;
-  int Ks[GMM_NKMAX];
-  unsigned long long off[GMM_NKMAX];  // bytes from a resample's block to the arrays of K index k
-  unsigned long long per_b;           // bytes of one resample's block
-  int* word;
-  State* st;
-  char* base;
-  const double* Xb;
-};
-
-__host__ __device__ inline int pad16(int K) { return (K + 15) & ~15; }
-__host__ __device__ inline size_t up256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
+using Args = BatchArgs<State>;
 
 // the one-hot responsibilities of every problem from the init labels, and the state reset
 template <class A>
@@ -167,11 +138,7 @@ __global__ __launch_bounds__(GT) void gmm_decide(A a, double tol, int max_iter) 
     return;
   }
   const auto pr = prob(a, p / a.nK, p % a.nK);
-  const int ntile = (a.m + 15) >> 4;
-  double t = 0.0;
-  for (int i = lane; i < ntile; i += 64) t += pr.part[i];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o);
+  const double t = sum_parts(pr.part, (a.m + 15) >> 4);
   if (lane == 0) {
     const double lower = t / a.m;
     const double change = lower - s.prev;
@@ -200,10 +167,7 @@ __global__ __launch_bounds__(GT) void gmm_pick(A a, int keep_best, int h_begin, 
   s.win = win;
   if (!win) return;
   s.best = s.lower;
-  const int64_t at = static_cast<int64_t>(p % a.nK) * ldo + h_begin + p / a.nK;
-  if (lower_bound) lower_bound[at] = s.lower;
-  if (n_iter) n_iter[at] = s.n_iter;
-  if (converged) converged[at] = static_cast<uint8_t>(s.converged);
+  put_scalars(a, p, h_begin, ldo, lower_bound, s.lower, n_iter, converged);
 }
 
 // the problem failed (sklearn's "ill-defined empirical covariance"): the batch is refused
@@ -211,56 +175,6 @@ __device__ inline void gmm_mark_failed(int* word, State& s) {
   if (!s.failed) atomicAdd(word + 1, 1);
   s.failed = 1;
   s.active = 0;
-}
-
-int launch_error(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    cc::set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return CC_ERR_HIP;
-  }
-  return CC_OK;
-}
-
-// the bounds both paths share: m, B, the values of K and the problem count
-bool batch_ok(int m, int B, const int* Ks, int nK) {
-  if (!Ks || m < 1 || m > (1 << 24) || B < 1 || B > 65535 || nK < 1 || nK > GMM_NKMAX) return false;
-  for (int k = 0; k < nK; ++k)
-    if (Ks[k] < 1 || Ks[k] > GMM_KMAX || Ks[k] > m) return false;
-  return static_cast<size_t>(B) * nK <= 65535;  // the problems are a grid's y extent
-}
-
-// the workspace: header, the states, then per resample the arrays of every K, where problem
-// (m, md, K) takes doubles(m, md, K) doubles
-template <class F>
-size_t layout(F doubles, int m, int md, int B, const int* Ks, int nK, void* ws, Args* a) {
-  const size_t states = up256(static_cast<size_t>(B) * nK * sizeof(State));
-  size_t per_b = 0;
-  for (int k = 0; k < nK; ++k) {
-    if (a) {
-      a->Ks[k] = Ks[k];
-      a->off[k] = per_b;
-    }
-    per_b += up256(8 * doubles(m, md, Ks[k]));
-  }
-  if (a) {
-    a->m = m;
-    a->md = md;
-    a->B = B;
-    a->nK = nK;
-    a->per_b = per_b;
-    a->word = static_cast<int*>(ws);
-    a->st = reinterpret_cast<State*>(static_cast<char*>(ws) + HEADER);
-    a->base = static_cast<char*>(ws) + HEADER + states;
-    a->Xb = nullptr;
-  }
-  return HEADER + states + static_cast<size_t>(B) * per_b;
-}
-
-int max_kp(const int* Ks, int nK) {
-  int v = 0;
-  for (int k = 0; k < nK; ++k) v = pad16(Ks[k]) > v ? pad16(Ks[k]) : v;
-  return v;
 }
 
 }  // namespace

@@ -24,6 +24,7 @@
 #include <string>
 
 #include "ccmi_internal.h"
+#include "launch_error.hpp"
 #include "linkage_shared.hpp"
 
 #pragma clang fp contract(off)  // every product and sum of this file is rounded separately
@@ -136,15 +137,6 @@ size_t hc_status_bytes(int B) { return align_up(static_cast<size_t>(B) * sizeof(
 size_t hc_state_bytes(int m, int B) { return align_up(static_cast<size_t>(B) * 2 * m * sizeof(int), HC_HDR_ALIGN); }
 size_t hc_links_bytes(int m, int B, int nK) {
   return static_cast<size_t>(B) * static_cast<size_t>(nK) * static_cast<size_t>(m) * sizeof(int);
-}
-
-int launch_error(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    cc::set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return CC_ERR_HIP;
-  }
-  return CC_OK;
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 // K14: batched multiplicative updates for the NMF base clusterer (nmf.py).
 //
 // A batch is B resamples x nK values of K = B * nK problems over the compact float64 rows
-// Xb [B][m][md] (cc_gmm_gather), X ~ W H with W [m][Kp] and H [Kp][md], Kp = K rounded up to 16 and
+// Xb [B][m][md], X ~ W H with W [m][Kp] and H [Kp][md], Kp = K rounded up to 16 and
 // the padding kept at 0.  One iteration of every active problem is two launches, ordered by the
 // stream:
 //   nmf_wstep   (row chunks x problems) one wave per 16-row tile: X H^T (inner length md) and
@@ -27,11 +27,15 @@
 //   error         per 16-row tile lane (q, c) adds, for the column slabs in order, its rows q, q + 4,
 //                 q + 8, q + 12 at column c, then a butterfly over the 64 lanes; per problem lane l
 //                 adds tiles l, l + 64, .. in order, then a butterfly over the 64 lanes
-#include "gmm_shared.hpp"
+//
+// The batch frame is batch_shared.hpp's: the arguments, the workspace layout and header, the row
+// grid and the tile sums.  cc_gmm_gather (gmm.hip) fills Xb, and cc_gmm_active reads the two header
+// words of this workspace as of the mixtures': both serve every row-batch clusterer under the
+// names they got first.
+#include "batch_shared.hpp"
 
 namespace {
 
-constexpr int ROW_CHUNKS = 128;  // most workgroups along the rows of one problem
 constexpr double NMF_EPS = 1.1920928955078125e-07;  // np.finfo(np.float32).eps
 
 struct NState {
@@ -39,16 +43,7 @@ struct NState {
   int n_iter, active, converged, win;
 };
 
-struct NArgs {
-  int m, md, B, nK;
-  int Ks[GMM_NKMAX];
-  unsigned long long off[GMM_NKMAX];  // bytes from a resample's block to the arrays of K index k
-  unsigned long long per_b;           // bytes of one resample's block
-  int* word;
-  NState* st;
-  char* base;
-  const double* Xb;
-};
+using Args = BatchArgs<NState>;
 
 // the arrays of one problem, in this order: W [m][Kp], H [Kp][md], HHt [Kp][Kp], WtW [Kp][Kp],
 // num [Kp][md] (W^T X), part [ceil(m / 16)]
@@ -63,7 +58,7 @@ __host__ __device__ inline size_t prob_doubles(int m, int md, int K) {
          static_cast<size_t>((m + 15) / 16);
 }
 
-__device__ inline Prob prob(const NArgs& a, int b, int k) {
+__device__ inline Prob prob(const Args& a, int b, int k) {
   Prob p;
   p.K = a.Ks[k];
   p.Kp = pad16(p.K);
@@ -75,10 +70,6 @@ __device__ inline Prob prob(const NArgs& a, int b, int k) {
   p.num = p.WtW + Kp * Kp;
   p.part = p.num + Kp * md;
   return p;
-}
-
-__device__ inline f64x4 mfma(double a, double b, f64x4 c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 
 // H H^T [Kp][Kp] of one problem, one wave per 16 x 16 tile; the whole workgroup calls it
@@ -101,19 +92,9 @@ __device__ inline void hht_tiles(const Prob& pr, int md) {
   }
 }
 
-// the sum of a problem's tile sums; the whole wave calls it and every lane gets the result
-__device__ inline double sum_parts(const double* part, int ntile) {
-  const int lane = threadIdx.x & 63;
-  double t = 0.0;
-  for (int i = lane; i < ntile; i += 64) t += part[i];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o);
-  return t;
-}
-
 // one init of every problem: avg = sqrt(mean(X) / K), W = avg |N_W|, H = avg |N_H| (the normals
 // [m][K] and [K][md] per K, concatenated, shared by the resamples), H H^T and the state
-__global__ __launch_bounds__(GT) void nmf_init(NArgs a, const double* __restrict__ NW, const double* __restrict__ NH) {
+__global__ __launch_bounds__(GT) void nmf_init(Args a, const double* __restrict__ NW, const double* __restrict__ NH) {
   __shared__ double red[GT];
   const int p = blockIdx.x, b = p / a.nK, k = p % a.nK, tid = threadIdx.x;
   const Prob pr = prob(a, b, k);
@@ -151,7 +132,7 @@ __global__ __launch_bounds__(GT) void nmf_init(NArgs a, const double* __restrict
 }
 
 // W *= (X H^T) / (W (H H^T)) of the active problems, one wave per 16-row tile
-__global__ __launch_bounds__(GT) void nmf_wstep(NArgs a) {
+__global__ __launch_bounds__(GT) void nmf_wstep(Args a) {
   extern __shared__ double lds[];
   const int p = blockIdx.y, b = p / a.nK, k = p % a.nK;
   if (!a.st[p].active) return;  // uniform over the workgroup
@@ -207,7 +188,7 @@ __global__ __launch_bounds__(GT) void nmf_wstep(NArgs a) {
 }
 
 // W^T W, W^T X, H *= (W^T X) / ((W^T W) H), H H^T and the iteration count of the active problems
-__global__ __launch_bounds__(GT) void nmf_hstep(NArgs a) {
+__global__ __launch_bounds__(GT) void nmf_hstep(Args a) {
   extern __shared__ double lds[];
   const int p = blockIdx.x, b = p / a.nK, k = p % a.nK;
   if (!a.st[p].active) return;  // uniform over the workgroup
@@ -281,7 +262,7 @@ __global__ __launch_bounds__(GT) void nmf_hstep(NArgs a) {
 }
 
 // the sum of (X - W H)^2 over every 16-row tile of the active problems (all: of every problem)
-__global__ __launch_bounds__(GT) void nmf_resid(NArgs a, int all) {
+__global__ __launch_bounds__(GT) void nmf_resid(Args a, int all) {
   const int p = blockIdx.y, b = p / a.nK, k = p % a.nK;
   if (!all && !a.st[p].active) return;  // uniform over the workgroup
   const Prob pr = prob(a, b, k);
@@ -324,7 +305,7 @@ __global__ __launch_bounds__(GT) void nmf_resid(NArgs a, int all) {
 // one wave per problem.  init: the error at init.  Otherwise, for a problem still active: at an
 // iteration that is a multiple of 10 (tol > 0) sklearn's test on the error, then max_iter; the
 // problems that go on are counted in the header word
-__global__ __launch_bounds__(GT) void nmf_decide(NArgs a, int init, double tol, int max_iter) {
+__global__ __launch_bounds__(GT) void nmf_decide(Args a, int init, double tol, int max_iter) {
   const int p = blockIdx.x * GW + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (p >= a.B * a.nK) return;
   NState& s = a.st[p];
@@ -349,7 +330,7 @@ __global__ __launch_bounds__(GT) void nmf_decide(NArgs a, int init, double tol, 
 }
 
 // one wave per problem: the final error, whether this init wins, and the winners' scalar outputs
-__global__ __launch_bounds__(GT) void nmf_pick(NArgs a, int keep_best, int h_begin, double* reconstruction_err,
+__global__ __launch_bounds__(GT) void nmf_pick(Args a, int keep_best, int h_begin, double* reconstruction_err,
                                                int* n_iter, uint8_t* converged, int64_t ldo) {
   const int p = blockIdx.x * GW + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (p >= a.B * a.nK) return;
@@ -362,14 +343,11 @@ __global__ __launch_bounds__(GT) void nmf_pick(NArgs a, int keep_best, int h_beg
   s.win = win;
   if (!win) return;
   s.best = err;
-  const int64_t at = static_cast<int64_t>(p % a.nK) * ldo + h_begin + p / a.nK;
-  if (reconstruction_err) reconstruction_err[at] = err;
-  if (n_iter) n_iter[at] = s.n_iter;
-  if (converged) converged[at] = static_cast<uint8_t>(s.converged);
+  put_scalars(a, p, h_begin, ldo, reconstruction_err, err, n_iter, converged);
 }
 
 // the labels of the problems whose init won: argmax_k W[r][k] sqrt((H H^T)[k][k]), first index
-__global__ __launch_bounds__(GT) void nmf_label(NArgs a, const int* __restrict__ idx, uint8_t* __restrict__ labels,
+__global__ __launch_bounds__(GT) void nmf_label(Args a, const int* __restrict__ idx, uint8_t* __restrict__ labels,
                                                 int64_t n, int64_t ldl, int h_begin) {
   __shared__ double norm[128];
   const int p = blockIdx.y, b = p / a.nK, k = p % a.nK;
@@ -395,64 +373,27 @@ __global__ __launch_bounds__(GT) void nmf_label(NArgs a, const int* __restrict__
   }
 }
 
-// K may exceed m and md
-bool shape_ok(int m, int md, int B, const int* Ks, int nK) {
-  if (!Ks || m < 1 || m > (1 << 24) || md < 1 || md > (1 << 20) || B < 1 || B > 65535 || nK < 1 || nK > GMM_NKMAX)
-    return false;
-  for (int k = 0; k < nK; ++k)
-    if (Ks[k] < 1 || Ks[k] > GMM_KMAX) return false;
-  return static_cast<size_t>(B) * nK <= 65535;  // the problems are a grid's y extent
-}
+constexpr int MD_MAX = 1 << 20;
 
-// the workspace: header, the states, then per resample the arrays of every K
-size_t layout(int m, int md, int B, const int* Ks, int nK, void* ws, NArgs* a) {
-  const size_t states = up256(static_cast<size_t>(B) * nK * sizeof(NState));
-  size_t per_b = 0;
-  for (int k = 0; k < nK; ++k) {
-    if (a) {
-      a->Ks[k] = Ks[k];
-      a->off[k] = per_b;
-    }
-    per_b += up256(8 * prob_doubles(m, md, Ks[k]));
-  }
-  if (a) {
-    a->m = m;
-    a->md = md;
-    a->B = B;
-    a->nK = nK;
-    a->per_b = per_b;
-    a->word = static_cast<int*>(ws);
-    a->st = reinterpret_cast<NState*>(static_cast<char*>(ws) + HEADER);
-    a->base = static_cast<char*>(ws) + HEADER + states;
-    a->Xb = nullptr;
-  }
-  return HEADER + states + static_cast<size_t>(B) * per_b;
+// batch_enter for this file's problems; K may exceed m and md
+bool enter(Args* a, bool ok, const double* Xb, int m, int md, int B, const int* Ks, int nK, void* ws, size_t ws_bytes,
+           const char* error) {
+  return batch_enter(a, prob_doubles, MD_MAX, false, ok, Xb, m, md, B, Ks, nK, ws, ws_bytes, error);
 }
-
-dim3 row_grid(int m, int B, int nK) {
-  const int ntile = (m + 15) / 16, chunks = (ntile + GW - 1) / GW;
-  return dim3(chunks < ROW_CHUNKS ? chunks : ROW_CHUNKS, B * nK);
-}
-
-size_t tile_lds(const int* Ks, int nK) { return static_cast<size_t>(GW) * max_kp(Ks, nK) * 16 * sizeof(double); }
 
 }  // namespace
 
 extern "C" size_t cc_nmf_workspace_bytes(int m, int md, int B, const int* Ks, int nK) {
-  if (!shape_ok(m, md, B, Ks, nK)) return 0;
-  return layout(m, md, B, Ks, nK, nullptr, nullptr);
+  if (!batch_ok(m, md, B, Ks, nK, MD_MAX, false)) return 0;
+  return layout<NState>(prob_doubles, m, md, B, Ks, nK, nullptr, nullptr);
 }
 
 extern "C" int cc_nmf_start(const double* Xb, int B, int m, int md, const int* Ks, int nK, const double* normals_w,
                             const double* normals_h, void* workspace, size_t ws_bytes, void* stream) {
-  if (!Xb || !normals_w || !normals_h || !workspace || !shape_ok(m, md, B, Ks, nK) ||
-      ws_bytes < cc_nmf_workspace_bytes(m, md, B, Ks, nK)) {
-    cc::set_error("cc_nmf_start: bad arguments (1 <= K <= 127, at most 127 values of K, B * nK <= 65535)");
+  Args a;
+  if (!enter(&a, normals_w && normals_h, Xb, m, md, B, Ks, nK, workspace, ws_bytes,
+             "cc_nmf_start: bad arguments (1 <= K <= 127, at most 127 values of K, B * nK <= 65535)"))
     return CC_ERR_ARG;
-  }
-  NArgs a;
-  layout(m, md, B, Ks, nK, workspace, &a);
-  a.Xb = Xb;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(workspace, 0, HEADER, st) != hipSuccess) return launch_error("cc_nmf_start");
   hipLaunchKernelGGL(nmf_init, dim3(B * nK), dim3(GT), 0, st, a, normals_w, normals_h);
@@ -463,14 +404,10 @@ extern "C" int cc_nmf_start(const double* Xb, int B, int m, int md, const int* K
 
 extern "C" int cc_nmf_steps(const double* Xb, int B, int m, int md, const int* Ks, int nK, int first, int count,
                             double tol, int max_iter, void* workspace, size_t ws_bytes, void* stream) {
-  if (!Xb || !workspace || !shape_ok(m, md, B, Ks, nK) || first < 1 || count < 0 || !(tol >= 0.0) || max_iter < 1 ||
-      ws_bytes < cc_nmf_workspace_bytes(m, md, B, Ks, nK)) {
-    cc::set_error("cc_nmf_steps: bad arguments");
+  Args a;
+  if (!enter(&a, first >= 1 && count >= 0 && tol >= 0.0 && max_iter >= 1, Xb, m, md, B, Ks, nK, workspace, ws_bytes,
+             "cc_nmf_steps: bad arguments"))
     return CC_ERR_ARG;
-  }
-  NArgs a;
-  layout(m, md, B, Ks, nK, workspace, &a);
-  a.Xb = Xb;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t lds = tile_lds(Ks, nK);
   for (int it = first; it < first + count && it <= max_iter; ++it) {
@@ -489,16 +426,11 @@ extern "C" int cc_nmf_finish(const double* Xb, const int* idx, int B, int m, int
                              int keep_best, int h_begin, uint8_t* labels, int64_t n, int64_t ldl,
                              double* reconstruction_err, int* n_iter, uint8_t* converged, int64_t ldo, void* workspace,
                              size_t ws_bytes, void* stream) {
-  if (!Xb || !idx || !labels || !workspace || !shape_ok(m, md, B, Ks, nK) || h_begin < 0 || n < 1 ||
-      ldl < static_cast<int64_t>(h_begin) + B ||
-      ((reconstruction_err || n_iter || converged) && ldo < static_cast<int64_t>(h_begin) + B) ||
-      ws_bytes < cc_nmf_workspace_bytes(m, md, B, Ks, nK)) {
-    cc::set_error("cc_nmf_finish: bad arguments");
+  Args a;
+  if (!enter(&a, idx && labels && n >= 1 && columns_ok(h_begin, B, ldl) &&
+                 (!(reconstruction_err || n_iter || converged) || columns_ok(h_begin, B, ldo)),
+             Xb, m, md, B, Ks, nK, workspace, ws_bytes, "cc_nmf_finish: bad arguments"))
     return CC_ERR_ARG;
-  }
-  NArgs a;
-  layout(m, md, B, Ks, nK, workspace, &a);
-  a.Xb = Xb;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(nmf_resid, row_grid(m, B, nK), dim3(GT), 0, st, a, 1);
   hipLaunchKernelGGL(nmf_pick, dim3((B * nK + GW - 1) / GW), dim3(GT), 0, st, a, keep_best, h_begin, reconstruction_err,

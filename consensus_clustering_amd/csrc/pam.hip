@@ -34,6 +34,7 @@
 #include <string>
 
 #include "ccmi_internal.h"
+#include "launch_error.hpp"
 
 #pragma clang fp contract(off)  // every difference and sum of this file is rounded separately
 
@@ -428,15 +429,6 @@ __global__ __launch_bounds__(PT) void labels_kernel(const double* __restrict__ D
   }
   if (medoids)
     for (int i = tid; i < Kmax; i += PT) medoids[p * Kmax + i] = i < K ? smed[i] : -1;
-}
-
-int launch_error(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    cc::set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return CC_ERR_HIP;
-  }
-  return CC_OK;
 }
 
 bool shape_ok(int B, int m, int nK, int Kmax) {

@@ -49,6 +49,7 @@
 #include <string>
 
 #include "ccmi_internal.h"
+#include "launch_error.hpp"
 
 #pragma clang fp contract(off)  // every product and sum of this file is rounded separately
 
@@ -315,15 +316,6 @@ __global__ __launch_bounds__(256) void tile_kernel(const T* __restrict__ Xall, i
         if (bi != bj) D[static_cast<int64_t>(j) * n + i] = v;
       }
     }
-}
-
-int launch_error(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    cc::set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return CC_ERR_HIP;
-  }
-  return CC_OK;
 }
 
 // the upper-triangle tiles of an n x n matrix, a grid's x extent; `what` names the entry point

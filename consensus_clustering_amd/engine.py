@@ -871,17 +871,89 @@ def _up256(v: int) -> int:
     return (int(v) + 255) & ~255
 
 
+def _rows_bytes(m: int, md: int, Ks, doubles) -> int:
+    """Device bytes one resample of a row batch needs: its compact float64 rows [m, md], its row and
+    column indices and per K the arrays of the problem, doubles(K, Kp) float64 values (Kp = K
+    rounded up to 16) rounded up to 256 bytes, and its 48-byte state."""
+    per = 8 * m * md + 4 * m + 4 * md
+    for K in Ks:
+        per += _up256(8 * doubles(int(K), (int(K) + 15) & ~15)) + 64
+    return per
+
+
+def _plan_rows(per: int, fixed: int, nh: int, nK: int, budget: int, who: str, m: int, md: int) -> int:
+    """min(nh, the resamples of `per` bytes each that fit the budget next to `fixed` bytes), at most
+    65535 problems a launch.  Raises when one resample does not fit."""
+    fit = (int(budget) - fixed) // per
+    if fit < 1:
+        raise ValueError(
+            f"workspace_budget = {int(budget)} bytes cannot hold the {who} clusterer: one resample "
+            f"of m = {int(m)} over {int(md)} features ({per + fixed} bytes) is needed")
+    return max(1, min(int(nh), int(fit), 65535 // nK))
+
+
+def _scalar_outputs(nK: int, labels: torch.Tensor, *outputs) -> int:
+    """ldo, the row length that the [nK, H] output tensors of (tensor or None, dtype) pairs share
+    (0 when all are None), after the asserts on them and on the label matrix [nK, n, Hpad]."""
+    assert labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous() and labels.shape[0] == nK
+    ldo = 0
+    for t, dt in outputs:
+        if t is not None:
+            assert t.dtype == dt and t.dim() == 2 and t.shape[0] == nK and t.is_contiguous()
+            assert ldo in (0, t.shape[1])
+            ldo = t.shape[1]
+    return ldo
+
+
+def _row_batches(X64, idx_d, cols_d, h0, h1, B):
+    """(a, rows, cols_b, Xb) for the resamples [a, a + len(rows)) of [h0, h1), B at a time: rows and
+    cols_b (None without cols_d) = the rows of idx_d and cols_d, and Xb [len(rows), m, md] =
+    X64[rows[b]][:, cols_b[b]] (cc_gmm_gather) in one buffer that every batch reuses.  A batch with
+    an index outside its range raises ValueError before anything is launched for it."""
+    assert X64.dtype == torch.float64 and X64.dim() == 2 and X64.is_contiguous() and X64.is_cuda
+    assert idx_d.dtype == torch.int32 and idx_d.dim() == 2
+    n, d = X64.shape
+    m = idx_d.shape[1]
+    md = d if cols_d is None else cols_d.shape[1]
+    st = stream_ptr(X64.device)
+    buf = torch.empty((B, m, md), dtype=torch.float64, device=X64.device)
+    for a in range(h0, h1, B):
+        rows = idx_d[a:min(a + B, h1)].contiguous()
+        nb = rows.shape[0]
+        # an entry outside its range would be read out of bounds by the gather: checked here, on the
+        # device tensors, before anything is launched
+        lo, hi = (int(v) for v in torch.aminmax(rows))
+        if lo < 0 or hi >= n:
+            raise ValueError(f"idx entries must lie in [0, {n}), got [{lo}, {hi}]")
+        cols_b = None
+        if cols_d is not None:
+            cols_b = cols_d[a:a + nb].contiguous()
+            assert cols_b.dtype == torch.int32 and cols_b.dim() == 2 and cols_b.shape[0] == nb
+            lo, hi = (int(v) for v in torch.aminmax(cols_b))
+            if lo < 0 or hi >= d:
+                raise ValueError(f"cols entries must lie in [0, {d}), got [{lo}, {hi}]")
+        Xb = buf[:nb]
+        with timed("cc_gmm_gather"):
+            _lib.call("cc_gmm_gather", X64.data_ptr(), n, d, rows.data_ptr(), _lib.ptr(cols_b), nb, m, md,
+                      Xb.data_ptr(), st)
+        yield a, rows, cols_b, Xb
+
+
+def _rows_call(X64, idx_d, cols_d, h0, h1, Ks, budget):
+    """(m, md, nh, Ks as ints, budget) of a *_labels call over rows; budget None: half the free memory."""
+    if budget is None:
+        budget = torch.cuda.mem_get_info(X64.device)[0] // 2
+    md = X64.shape[1] if cols_d is None else cols_d.shape[1]
+    return idx_d.shape[1], md, h1 - h0, [int(K) for K in Ks], budget
+
+
 def gmm_bytes(m: int, md: int, Ks) -> int:
     """Device bytes one resample of a GMM batch needs: its compact float64 rows [m, md], its row and
     column indices and per K (Kp = K rounded up to 16) the responsibilities [m, Kp], the M-step
     sums [Kp, 2 md + 1], the E-step's operand image [Kp, 2 md], three constants per component, the
     16-row tile sums and the problem's 48-byte state: cc_gmm_workspace_bytes plus the rows."""
     m, md = int(m), int(md)
-    per = 8 * m * md + 4 * m + 4 * md
-    for K in Ks:
-        Kp = (int(K) + 15) & ~15
-        per += _up256(8 * (m * Kp + Kp * (2 * md + 1) + Kp * 2 * md + 3 * Kp + (m + 15) // 16)) + 64
-    return per
+    return _rows_bytes(m, md, Ks, lambda K, Kp: m * Kp + Kp * (2 * md + 1) + Kp * 2 * md + 3 * Kp + (m + 15) // 16)
 
 
 GMM_FULL_MD_MAX = 128  # the most features of the full-covariance kernels (csrc/gmm_full.hip)
@@ -894,12 +966,8 @@ def gmm_full_bytes(m: int, md: int, Ks) -> int:
     [Kp, md], three constants per component, the 16-row tile sums and the state:
     cc_gmm_full_workspace_bytes plus the rows."""
     m, md = int(m), int(md)
-    per = 8 * m * md + 4 * m + 4 * md
-    for K in Ks:
-        K = int(K)
-        Kp = (K + 15) & ~15
-        per += _up256(8 * (m * Kp + Kp * (md + 1) + Kp * md + K * md * md + Kp * md + 3 * Kp + (m + 15) // 16)) + 64
-    return per
+    return _rows_bytes(m, md, Ks, lambda K, Kp: (m * Kp + Kp * (md + 1) + Kp * md + K * md * md + Kp * md + 3 * Kp
+                                                 + (m + 15) // 16))
 
 
 def gmm_plan(n: int, m: int, nh: int, Ks, md: int, budget: int, covariance: str = 'diag') -> int:
@@ -909,13 +977,7 @@ def gmm_plan(n: int, m: int, nh: int, Ks, md: int, budget: int, covariance: str 
     resample does not fit."""
     nK = max(len(Ks), 1)
     per = (gmm_full_bytes if covariance == 'full' else gmm_bytes)(m, md, Ks) + nK * int(n)
-    fixed = 1024 + 127 * nK * int(n)
-    fit = (int(budget) - fixed) // per
-    if fit < 1:
-        raise ValueError(
-            f"workspace_budget = {int(budget)} bytes cannot hold the GMM clusterer: one resample "
-            f"of m = {int(m)} over {int(md)} features ({per + fixed} bytes) is needed")
-    return max(1, min(int(nh), int(fit), 65535 // nK))
+    return _plan_rows(per, 1024 + 127 * nK * int(n), nh, nK, budget, "GMM", m, md)
 
 
 def gmm_full_plan(n: int, m: int, nh: int, Ks, md: int, budget: int) -> int:
@@ -940,55 +1002,22 @@ def gmm_workspace(m: int, md: int, B: int, Ks_h: np.ndarray, device, covariance:
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
-def gmm_batch(X64: torch.Tensor, rows: torch.Tensor, cols_b, Ks, h_begin: int, labels: torch.Tensor,
-              n_init: int = 1, seed: int = 0, tol: float = 1e-3, reg_covar: float = 1e-6, max_iter: int = 100,
-              lower_bound: torch.Tensor = None, n_iter: torch.Tensor = None, converged: torch.Tensor = None,
-              ws: torch.Tensor = None, budget: int = None, covariance: str = 'diag') -> int:
-    """GMM (covariance 'diag') or FullGMM ('full': the cc_gmm_full_ entry points below, md <= 128)
-    (n_components=K, n_init, random_state=seed, tol, reg_covar, max_iter) of every (resample b
-    of rows [B, m], K) over X64[rows[b]][:, cols_b[b]] (cols_b None: all columns): cc_gmm_gather,
-    then per init the k-means labels of the float64 engine (BatchedKMeans.run_f64 with
-    kpp_init = (init, n_init)), cc_gmm_start, cc_gmm_em_step until cc_gmm_active reads 0 or
-    max_iter iterations ran, and cc_gmm_finish into labels[k, rows[b, r], h_begin + b] (uint8
-    [nK, n, Hpad]) and lower_bound / n_iter / converged ([nK, H], at column h_begin + b) where the
-    init is the best so far.  budget: the workspace budget of the k-means fits.
-    Returns the EM iterations launched; raises IllDefinedMixture as sklearn does."""
+def gmm_batch(X64, rows, cols_b, Xb, Ks_h, h_begin, labels, ws, n_init, seed, tol, reg_covar, max_iter,
+              lower_bound, n_iter, converged, ldo, budget, covariance) -> int:
+    """One batch of gmm_labels, (a, rows, cols_b, Xb) of _row_batches: per init the k-means labels
+    of the float64 engine (BatchedKMeans.run_f64 with kpp_init = (init, n_init)), cc_gmm_start (cc_gmm_full_start under covariance 'full', and so on),
+    cc_gmm_em_step until cc_gmm_active reads 0 or max_iter iterations ran, and cc_gmm_finish into
+    labels[k, rows[b, r], h_begin + b] and lower_bound / n_iter / converged ([nK, ldo], at column
+    h_begin + b) where the init is the best so far.  budget: the workspace budget of the k-means
+    fits.  Returns the EM iterations launched; raises IllDefinedMixture as sklearn does."""
     from .kmeans import BatchedKMeans
 
-    assert X64.dtype == torch.float64 and X64.dim() == 2 and X64.is_contiguous() and X64.is_cuda
-    assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.is_contiguous()
-    n, d = X64.shape
-    B, m = rows.shape
-    dev = X64.device
-    md = d if cols_b is None else cols_b.shape[1]
-    Ks_h = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
-    nK = len(Ks_h)
-    assert labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous() and labels.shape[0] == nK
-    ldo = 0
-    for t, dt in ((lower_bound, torch.float64), (n_iter, torch.int32), (converged, torch.uint8)):
-        if t is not None:
-            assert t.dtype == dt and t.dim() == 2 and t.shape[0] == nK and t.is_contiguous()
-            assert ldo in (0, t.shape[1])
-            ldo = t.shape[1]
-    # an entry outside its range would be read out of bounds by the gather: checked here, on the
-    # device tensors, before anything is launched
-    lo, hi = (int(v) for v in torch.aminmax(rows))
-    if lo < 0 or hi >= n:
-        raise ValueError(f"idx entries must lie in [0, {n}), got [{lo}, {hi}]")
-    if cols_b is not None:
-        assert cols_b.dtype == torch.int32 and cols_b.dim() == 2 and cols_b.shape[0] == B and cols_b.is_contiguous()
-        lo, hi = (int(v) for v in torch.aminmax(cols_b))
-        if lo < 0 or hi >= d:
-            raise ValueError(f"cols entries must lie in [0, {d}), got [{lo}, {hi}]")
-    if ws is None:
-        ws = gmm_workspace(m, md, B, Ks_h, dev, covariance)
+    n = X64.shape[0]
+    B, m, md = Xb.shape
     start, em_step, finish = (_gmm_entry(covariance, name) for name in ("start", "em_step", "finish"))
-    st = stream_ptr(dev)
-    Xb = torch.empty((B, m, md), dtype=torch.float64, device=dev)
-    with timed("cc_gmm_gather"):
-        _lib.call("cc_gmm_gather", X64.data_ptr(), n, d, rows.data_ptr(), _lib.ptr(cols_b), B, m, md, Xb.data_ptr(), st)
-    shape = (B, m, md, Ks_h.ctypes.data, nK)
-    lab = torch.empty((nK, n, pad_h(B)), dtype=torch.uint8, device=dev)  # each init's k-means labels
+    st = stream_ptr(X64.device)
+    shape = (B, m, md, Ks_h.ctypes.data, len(Ks_h))
+    lab = torch.empty((len(Ks_h), n, pad_h(B)), dtype=torch.uint8, device=X64.device)  # each init's k-means labels
     iterations = 0
     active, failed = ctypes.c_int(0), ctypes.c_int(0)
     for init in range(int(n_init)):
@@ -997,8 +1026,8 @@ def gmm_batch(X64: torch.Tensor, rows: torch.Tensor, cols_b, Ks, h_begin: int, l
                                workspace_budget=budget)
             bk.run_f64(X64, rows, n, B, m, 0, B, lab, cols_d=cols_b, kpp_init=(init, int(n_init)))
         with timed("cc_gmm_start"):
-            _lib.call(start, Xb.data_ptr(), rows.data_ptr(), B, m, md, Ks_h.ctypes.data, nK, lab.data_ptr(),
-                      n, lab.shape[2], 0, float(reg_covar), ws.data_ptr(), ws.numel(), st)
+            _lib.call(start, Xb.data_ptr(), rows.data_ptr(), *shape, lab.data_ptr(), n, lab.shape[2], 0,
+                      float(reg_covar), ws.data_ptr(), ws.numel(), st)
         with timed("cc_gmm_em"):
             for _ in range(int(max_iter)):
                 _lib.call(em_step, Xb.data_ptr(), *shape, float(tol), float(reg_covar), int(max_iter),
@@ -1021,20 +1050,15 @@ def gmm_labels(X64: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, lab
                max_iter: int = 100, cols_d: torch.Tensor = None, lower_bound: torch.Tensor = None,
                n_iter: torch.Tensor = None, converged: torch.Tensor = None, covariance: str = 'diag') -> dict:
     """Fill labels[k, idx[h, r], h] for h in [h0, h1) and every K of Ks with GMM(n_components=K, ...)
-    (covariance 'diag') or FullGMM(n_components=K, ...) ('full')
+    (covariance 'diag') or FullGMM(n_components=K, ...) ('full': the cc_gmm_full_ entry points,
+    md <= 128), with n_init, random_state=seed, tol, reg_covar and max_iter,
     over X64[idx[h]] (float64 [n, d], device), under feature subsampling over X64[idx[h]][:, cols[h]]
     (cols_d int32 [H, md], device, indexed by the global h like idx_d).  budget: device bytes for the
     batches (default: half the free memory); lower_bound / n_iter / converged: optional [nK, H]
     device tensors filled at the columns [h0, h1).  Returns dict(route='batched', batch, launches,
     em_iterations, inits)."""
-    n, d = X64.shape
-    dev = X64.device
-    m = idx_d.shape[1]
-    md = d if cols_d is None else cols_d.shape[1]
-    nh = h1 - h0
-    Ks = [int(K) for K in Ks]
-    if budget is None:
-        budget = torch.cuda.mem_get_info(dev)[0] // 2
+    n, dev = X64.shape[0], X64.device
+    m, md, nh, Ks, budget = _rows_call(X64, idx_d, cols_d, h0, h1, Ks, budget)
     _gmm_entry(covariance, "start")
     B = gmm_plan(n, m, max(nh, 1), Ks, md, budget, covariance)
     stats = dict(route='batched', batch=B, launches=0, em_iterations=0, inits=int(n_init))
@@ -1045,13 +1069,13 @@ def gmm_labels(X64: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, lab
     if min(Ks) < 1 or max(Ks) > m:
         raise ValueError(f"every K must lie in [1, m = {m}], got {Ks}")
     Ks_h = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
+    ldo = _scalar_outputs(len(Ks), labels, (lower_bound, torch.float64), (n_iter, torch.int32),
+                          (converged, torch.uint8))
     ws = gmm_workspace(m, md, B, Ks_h, dev, covariance)
-    for a in range(h0, h1, B):
-        b = min(a + B, h1)
-        stats['em_iterations'] += gmm_batch(
-            X64, idx_d[a:b].contiguous(), None if cols_d is None else cols_d[a:b].contiguous(), Ks, a, labels,
-            n_init, seed, tol, reg_covar, max_iter, lower_bound, n_iter, converged, ws=ws, budget=budget,
-            covariance=covariance)
+    for a, rows, cols_b, Xb in _row_batches(X64, idx_d, cols_d, h0, h1, B):
+        stats['em_iterations'] += gmm_batch(X64, rows, cols_b, Xb, Ks_h, a, labels, ws, n_init, seed, tol,
+                                            reg_covar, max_iter, lower_bound, n_iter, converged, ldo, budget,
+                                            covariance)
         stats['launches'] += 1
     return stats
 
@@ -1064,11 +1088,7 @@ def nmf_bytes(m: int, md: int, Ks) -> int:
     and W^T W [Kp, Kp] each, the 16-row tile sums of the error and the problem's 48-byte state:
     cc_nmf_workspace_bytes plus the rows."""
     m, md = int(m), int(md)
-    per = 8 * m * md + 4 * m + 4 * md
-    for K in Ks:
-        Kp = (int(K) + 15) & ~15
-        per += _up256(8 * (m * Kp + 2 * Kp * md + 2 * Kp * Kp + (m + 15) // 16)) + 64
-    return per
+    return _rows_bytes(m, md, Ks, lambda K, Kp: m * Kp + 2 * Kp * md + 2 * Kp * Kp + (m + 15) // 16)
 
 
 def nmf_plan(n: int, m: int, nh: int, Ks, md: int, budget: int, n_init: int = 1) -> int:
@@ -1076,15 +1096,8 @@ def nmf_plan(n: int, m: int, nh: int, Ks, md: int, budget: int, n_init: int = 1)
     to the normals of every init (float64, (m + md) * sum(Ks) values an init, shared by the
     resamples), at most nh and at most 65535 problems a launch.  Raises when one resample does not
     fit."""
-    nK = max(len(Ks), 1)
-    per = nmf_bytes(m, md, Ks)
     fixed = 1024 + 8 * int(n_init) * (int(m) + int(md)) * sum(int(K) for K in Ks)
-    fit = (int(budget) - fixed) // per
-    if fit < 1:
-        raise ValueError(
-            f"workspace_budget = {int(budget)} bytes cannot hold the NMF clusterer: one resample "
-            f"of m = {int(m)} over {int(md)} features ({per + fixed} bytes) is needed")
-    return max(1, min(int(nh), int(fit), 65535 // nK))
+    return _plan_rows(nmf_bytes(m, md, Ks), fixed, nh, max(len(Ks), 1), budget, "NMF", m, md)
 
 
 def nmf_workspace(m: int, md: int, B: int, Ks_h: np.ndarray, device) -> torch.Tensor:
@@ -1117,52 +1130,20 @@ def nmf_normals(seed: int, m: int, md: int, Ks, n_init: int, device):
 NMF_TEST_EVERY = 10  # sklearn's stopping test runs at the iterations that are multiples of 10
 
 
-def nmf_batch(X64: torch.Tensor, rows: torch.Tensor, cols_b, Ks, h_begin: int, labels: torch.Tensor, normals,
-              tol: float = 1e-4, max_iter: int = 200, reconstruction_err: torch.Tensor = None,
-              n_iter: torch.Tensor = None, converged: torch.Tensor = None, ws: torch.Tensor = None) -> int:
-    """NMF(n_components=K, n_init, tol, max_iter) of every (resample b of rows [B, m], K) over
-    X64[rows[b]][:, cols_b[b]] (cols_b None: all columns) from normals = nmf_normals(...), whose
-    first extent is n_init: cc_gmm_gather, then per init cc_nmf_start, cc_nmf_steps ten iterations a
-    call until cc_gmm_active reads 0 (one synchronisation per stopping test), and cc_nmf_finish
-    into labels[k, rows[b, r], h_begin + b] (uint8 [nK, n, Hpad]) and reconstruction_err / n_iter /
-    converged ([nK, H], at column h_begin + b) where the init is the best so far.  Returns the
-    iterations launched."""
-    assert X64.dtype == torch.float64 and X64.dim() == 2 and X64.is_contiguous() and X64.is_cuda
-    assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.is_contiguous()
-    n, d = X64.shape
-    B, m = rows.shape
-    dev = X64.device
-    md = d if cols_b is None else cols_b.shape[1]
-    Ks_h = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
-    nK = len(Ks_h)
-    assert labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous() and labels.shape[0] == nK
+def nmf_batch(rows, Xb, Ks_h, h_begin, labels, normals, ws, tol, max_iter, reconstruction_err, n_iter, converged,
+              ldo) -> int:
+    """One batch of nmf_labels, (a, rows, _, Xb) of _row_batches, from normals = nmf_normals(...),
+    whose first extent is n_init: per init cc_nmf_start, cc_nmf_steps ten iterations a call until
+    cc_gmm_active reads 0 (one synchronisation per stopping test), and cc_nmf_finish into
+    labels[k, rows[b, r], h_begin + b] and reconstruction_err / n_iter / converged ([nK, ldo], at
+    column h_begin + b) where the init is the best so far.  Returns the iterations launched."""
+    B, m, md = Xb.shape
     NW, NH = normals
     sumK = int(Ks_h.sum())
     for t, width in ((NW, m * sumK), (NH, md * sumK)):
         assert t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == width and t.is_contiguous() and t.is_cuda
-    ldo = 0
-    for t, dt in ((reconstruction_err, torch.float64), (n_iter, torch.int32), (converged, torch.uint8)):
-        if t is not None:
-            assert t.dtype == dt and t.dim() == 2 and t.shape[0] == nK and t.is_contiguous()
-            assert ldo in (0, t.shape[1])
-            ldo = t.shape[1]
-    # an entry outside its range would be read out of bounds by the gather: checked here, on the
-    # device tensors, before anything is launched
-    lo, hi = (int(v) for v in torch.aminmax(rows))
-    if lo < 0 or hi >= n:
-        raise ValueError(f"idx entries must lie in [0, {n}), got [{lo}, {hi}]")
-    if cols_b is not None:
-        assert cols_b.dtype == torch.int32 and cols_b.dim() == 2 and cols_b.shape[0] == B and cols_b.is_contiguous()
-        lo, hi = (int(v) for v in torch.aminmax(cols_b))
-        if lo < 0 or hi >= d:
-            raise ValueError(f"cols entries must lie in [0, {d}), got [{lo}, {hi}]")
-    if ws is None:
-        ws = nmf_workspace(m, md, B, Ks_h, dev)
-    st = stream_ptr(dev)
-    Xb = torch.empty((B, m, md), dtype=torch.float64, device=dev)
-    with timed("cc_gmm_gather"):
-        _lib.call("cc_gmm_gather", X64.data_ptr(), n, d, rows.data_ptr(), _lib.ptr(cols_b), B, m, md, Xb.data_ptr(), st)
-    shape = (B, m, md, Ks_h.ctypes.data, nK)
+    st = stream_ptr(Xb.device)
+    shape = (B, m, md, Ks_h.ctypes.data, len(Ks_h))
     iterations = 0
     active, failed = ctypes.c_int(0), ctypes.c_int(0)
     max_iter = int(max_iter)
@@ -1200,14 +1181,8 @@ def nmf_labels(X64: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, lab
     call.  budget: device bytes for the batches (default: half the free memory);
     reconstruction_err / n_iter / converged: optional [nK, H] device tensors filled at the columns
     [h0, h1).  Returns dict(route='batched', batch, launches, iterations, inits)."""
-    n, d = X64.shape
-    dev = X64.device
-    m = idx_d.shape[1]
-    md = d if cols_d is None else cols_d.shape[1]
-    nh = h1 - h0
-    Ks = [int(K) for K in Ks]
-    if budget is None:
-        budget = torch.cuda.mem_get_info(dev)[0] // 2
+    n, dev = X64.shape[0], X64.device
+    m, md, nh, Ks, budget = _rows_call(X64, idx_d, cols_d, h0, h1, Ks, budget)
     B = nmf_plan(n, m, max(nh, 1), Ks, md, budget, n_init)
     stats = dict(route='batched', batch=B, launches=0, iterations=0, inits=int(n_init))
     if cols_d is not None:
@@ -1217,13 +1192,13 @@ def nmf_labels(X64: torch.Tensor, idx_d: torch.Tensor, h0: int, h1: int, Ks, lab
     if min(Ks) < 1 or max(Ks) > 127:
         raise ValueError(f"every K must lie in [1, 127], got {Ks}")
     Ks_h = np.ascontiguousarray(np.asarray(Ks, dtype=np.int32))
+    ldo = _scalar_outputs(len(Ks), labels, (reconstruction_err, torch.float64), (n_iter, torch.int32),
+                          (converged, torch.uint8))
     ws = nmf_workspace(m, md, B, Ks_h, dev)
     with timed("nmf_normals"):
         normals = nmf_normals(int(seed), m, md, Ks, n_init, dev)
-    for a in range(h0, h1, B):
-        b = min(a + B, h1)
-        stats['iterations'] += nmf_batch(
-            X64, idx_d[a:b].contiguous(), None if cols_d is None else cols_d[a:b].contiguous(), Ks, a, labels,
-            normals, tol, max_iter, reconstruction_err, n_iter, converged, ws=ws)
+    for a, rows, _, Xb in _row_batches(X64, idx_d, cols_d, h0, h1, B):
+        stats['iterations'] += nmf_batch(rows, Xb, Ks_h, a, labels, normals, ws, tol, max_iter, reconstruction_err,
+                                         n_iter, converged, ldo)
         stats['launches'] += 1
     return stats

@@ -407,7 +407,8 @@ size_t cc_gmm_workspace_bytes(int m, int md, int B, const int* Ks, int nK);
 
 /* Xb[b][r][c] = X[idx[b][r]][cols ? cols[b][c] : c]: the rows of B resamples under their own
  * columns.  X [n][d] float64; idx [B][m] int32 and cols (NULL = all columns, md = d; else [B][md]
- * int32) on the device, read as given: the caller checks their ranges. */
+ * int32) on the device, read as given: the caller checks their ranges.  It serves every row-batch
+ * clusterer (GMM, FullGMM, NMF) under the name it got first. */
 int cc_gmm_gather(const double* X, int64_t n, int d, const int* idx, const int* cols, int B, int m, int md,
                   double* Xb, void* stream);
 
@@ -432,7 +433,10 @@ int cc_gmm_em_step(const double* Xb, int B, int m, int md, const int* Ks, int nK
 
 /* Synchronises `stream` and stores in *active (host) how many problems the last cc_gmm_em_step
  * left active (0 = every problem is finished) and in *failed (host, may be NULL) how many
- * problems of the batch have failed since cc_gmm_start. */
+ * problems of the batch have failed since cc_gmm_start.  It reads only the two header words that
+ * the workspaces of every row-batch clusterer share (cc_gmm_workspace_bytes,
+ * cc_gmm_full_workspace_bytes, cc_nmf_workspace_bytes), so it serves all three: after
+ * cc_gmm_full_em_step and cc_nmf_steps as after cc_gmm_em_step. */
 int cc_gmm_active(const void* workspace, int* active, int* failed, void* stream);
 
 /* The results of one init: with keep_best = 0 (the first init) of every problem, else of the
